@@ -16,11 +16,17 @@ rows fixed); the keyless Q6 partial state is exchanged with an RCCL all_reduce
 over xGMI, mirroring the reference's partial->final aggregation exchange.
 
 Output: ONE JSON line from rank 0 per the driver contract, including
-`roofline` (achieved HBM GB/s of the scan kernel from HIP events on its
-launch stream vs the 8 TB/s chip peak) and `cpu_baseline` (the CPU oracle —
-a faithful restatement of the reference's WholeStageCodegen loop — timed on
-the host cores over a bounded sample; the reference itself is JVM-only and
-cannot run here: BASELINE.md).
+`ms_per_step` (wall milliseconds per timed step; --steps sets their number)
+and `roofline` (achieved HBM GB/s of the scan kernel from the HIP events the
+timed steps already record on its launch stream, vs the 8 TB/s chip peak).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full
+adds `cpu_baseline` (the CPU oracle — a faithful restatement of the
+reference's WholeStageCodegen loop — timed on the host cores over a bounded
+sample; the reference itself is JVM-only and cannot run here: BASELINE.md);
+without --full that field is null.  --dump-outputs DIR writes the result
+rows of the last timed step as DIR/values.npy, plus DIR/keys.npy when the
+result is grouped (see dump_outputs); inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -307,21 +313,78 @@ def cpu_baseline_leg(workload, seed, target_seconds=10.0, sample_rows=None):
     }
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_KEY_BYTES = 24          # longest key text: a decimal int64 is 20 chars
+DUMP_KEY_WORDS = DUMP_KEY_BYTES // 6
+
+
+def dump_outputs(dirname, rows, seed):
+    """Write the result rows a caller of the timed path receives — a list of
+    (group-key tuple, aggregate values) — as float64 arrays:
+      values.npy  (nrows, naggs)   NULL aggregates as NaN
+      keys.npy    (nrows, ngroup, 4) each key's text, zero-padded to 24
+                  bytes and packed 6 bytes (big-endian) per float64 so it is
+                  exact; NULL keys as NaN; written only for grouped
+                  results (a keyless result such as Q6 has no keys)
+    Rows are sorted by key so two builds compare row for row whatever order
+    the hash aggregate emitted them in.  A result set over the 64 MB budget
+    is cut to a fixed, seeded sample of the sorted rows."""
+    rows = sorted(rows, key=lambda r: tuple((k is None, k or "")
+                                            for k in r[0]))
+    ngroup = len(rows[0][0]) if rows else 0
+    naggs = len(rows[0][1]) if rows else 0
+    row_bytes = 8 * (naggs + ngroup * DUMP_KEY_WORDS)
+    cap = DUMP_BUDGET_BYTES // max(1, row_bytes)
+    if len(rows) > cap:
+        pick = np.sort(np.random.default_rng(seed).choice(
+            len(rows), size=cap, replace=False))
+        rows = [rows[i] for i in pick]
+    values = np.array([[np.nan if v is None else v for v in vals]
+                       for _, vals in rows], dtype=np.float64)
+    values = values.reshape(len(rows), naggs)
+    keys = np.full((len(rows), ngroup, DUMP_KEY_WORDS), np.nan)
+    for r, (ks, _) in enumerate(rows):
+        for g, k in enumerate(ks):
+            if k is None:
+                continue
+            raw = k.encode()[:DUMP_KEY_BYTES].ljust(DUMP_KEY_BYTES, b"\0")
+            keys[r, g] = [int.from_bytes(raw[i:i + 6], "big")
+                          for i in range(0, DUMP_KEY_BYTES, 6)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "values.npy"), values)
+    keys_path = os.path.join(dirname, "keys.npy")
+    if ngroup:
+        np.save(keys_path, keys)
+    elif os.path.exists(keys_path):
+        os.remove(keys_path)      # a keyless result has no key array
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20,
+                    help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="tpch_q6_lineitem_sf100",
                     choices=sorted(WORKLOADS))
     ap.add_argument("--rows", type=int, default=0,
                     help="override rows per GPU")
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not "
+                         "need (the CPU-oracle baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU-oracle baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result rows to "
+                         "DIR/values.npy, and DIR/keys.npy when grouped "
+                         "(float64)")
     ap.add_argument("--no-a2a", action="store_true",
                     help="use all_gather instead of the key-sharded "
                          "all-to-all for the grouped exchange (N>1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -377,7 +440,9 @@ def main():
     # its operator loop (result iteration) — count groups once, untimed
     heavy_result = args.workload == "sparse_group_sf10"
 
-    def step():
+    kept = {}
+
+    def step(keep=False):
         q = eng.query(plan)
         q.wait()
         km = q.kernel_ms()
@@ -433,7 +498,10 @@ def main():
                 blocks = gathered.cpu().numpy()
                 q.merge_host(np.ascontiguousarray(blocks), n, world)
         rows = q.rows() if not heavy_result else None
-        q.close()
+        if keep:
+            kept["q"] = q     # --dump-outputs reads its rows after the timer
+        else:
+            q.close()
         return rows, km
 
     n_result_rows = {"v": 0}
@@ -458,8 +526,9 @@ def main():
     barrier_sync()
     kms = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        result, km = step()
+    keep_last = heavy_result and args.dump_outputs is not None
+    for i in range(args.steps):
+        result, km = step(keep_last and i == args.steps - 1)
         if km > 0:
             kms.append(km)
     barrier_sync()
@@ -470,6 +539,12 @@ def main():
                            device=f"cuda:{local_rank}")
         dist.all_reduce(e_t, op=dist.ReduceOp.MAX)
         elapsed = float(e_t.cpu())
+
+    if "q" in kept:
+        result = kept["q"].rows()
+        kept.pop("q").close()
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, result, args.seed)
 
     ms_per_step = elapsed * 1000.0 / args.steps
     value = total_rows * args.steps / elapsed
@@ -496,7 +571,7 @@ def main():
                 "kernel_ms": round(avg_ms, 4),
             }
         cpu_baseline = None
-        if world == 1 and not args.no_cpu_baseline and (
+        if args.full and world == 1 and not args.no_cpu_baseline and (
                 "lineitem" in args.workload or "mut" in args.workload
                 or args.workload in ("config1_sum_where", "star_join_sf10",
                                      "sparse_group_sf10")):

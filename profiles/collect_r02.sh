@@ -41,7 +41,7 @@ B=$OUT/bench_r02_final.jsonl
 for W in tpch_q6_lineitem_sf100 tpch_q1_lineitem_sf100 tpch_q6_lineitem_sf10 \
          tpch_q1_lineitem_sf10 tpch_q6_mut_sf10 star_join_sf10 \
          config1_sum_where sparse_group_sf10; do
-  timeout 900 python bench.py --workload "$W" --steps 10 --warmup 3 \
+  timeout 900 python bench.py --full --workload "$W" --steps 10 --warmup 3 \
       >> "$B" 2> "$OUT/bench_$W.err"
 done
 echo DONE

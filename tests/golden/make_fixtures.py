@@ -1,7 +1,7 @@
 """Generate the committed golden fixtures under tests/golden/.
 
-Run in the build container (where /root/reference exists):
-    python tests/golden/make_fixtures.py
+Run with a checkout of the reference (SnappyDataInc/snappydata) at hand:
+    python tests/golden/make_fixtures.py <reference>/tests/common/src/main/resources/TPCH
 
 Outputs (committed):
   - vectors.npz        : encoder byte-layout pins — inputs + expected blobs for
@@ -13,7 +13,7 @@ Outputs (committed):
                          (tests/common/src/main/resources/TPCH/, 30,201 rows)
                          encoded into reference-format column batches, so GPU
                          parity tests can reproduce Snappy_1.out/Snappy_6.out
-                         on boxes without /root/reference.
+                         without the reference tree.
 """
 import json
 import os
@@ -140,8 +140,8 @@ def read_batches(path):
     return out
 
 
-def make_lineitem():
-    data = tu.load_lineitem_tbl()
+def make_lineitem(tpch_dir):
+    data = tu.load_lineitem_tbl(os.path.join(tpch_dir, "lineitem.tbl"))
     batches = tu.encode_lineitem_batches(data, 4096)
     write_batches(os.path.join(HERE, "lineitem_batches.bin"), batches)
     n = sum(b[0] for b in batches)
@@ -150,4 +150,4 @@ def make_lineitem():
 
 if __name__ == "__main__":
     make_vectors()
-    make_lineitem()
+    make_lineitem(sys.argv[1])

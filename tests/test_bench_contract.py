@@ -40,6 +40,32 @@ def test_traffic_json_committed_and_sane():
     assert 39 < cal["tpch_q1_lineitem_sf10"]["bytes_per_row"] < 42
 
 
+def test_dump_outputs_layout(tmp_path):
+    """--dump-outputs arrays: float64, key-sorted, keys exact (an int64 key's
+    decimal text survives where a float64 cast would not), NULLs as NaN."""
+    rows = [(("R", "F"), [2.5, None]),
+            (("A", None), [1.0, 7.0]),
+            (("-4611686018427387903", "x"), [0.5, 3.0])]
+    bench.dump_outputs(str(tmp_path), rows, seed=42)
+    vals = np.load(tmp_path / "values.npy")
+    keys = np.load(tmp_path / "keys.npy")
+    assert vals.dtype == np.float64 and keys.dtype == np.float64
+    assert vals.shape == (3, 2) and keys.shape == (3, 2, 4)
+    assert vals[:, 0].tolist() == [0.5, 1.0, 2.5]        # sorted by key
+    assert np.isnan(vals[2, 1]) and np.isnan(keys[1, 1]).all()
+
+    def text(words):
+        raw = b"".join(int(w).to_bytes(6, "big") for w in words)
+        return raw.rstrip(b"\0").decode()
+    assert text(keys[0, 0]) == "-4611686018427387903"
+    assert text(keys[2, 0]) == "R" and text(keys[2, 1]) == "F"
+    # keyless result (the default Q6 workload): one row and no key array —
+    # no empty file, and none left over from an earlier dump either
+    bench.dump_outputs(str(tmp_path), [((), [596503.1903])], seed=42)
+    assert np.load(tmp_path / "values.npy").tolist() == [[596503.1903]]
+    assert not (tmp_path / "keys.npy").exists()
+
+
 def test_cpu_baseline_leg_contract():
     r = bench.cpu_baseline_leg("tpch_q6_lineitem_sf10", 42, target_seconds=0.3,
                                sample_rows=2_400_000)

@@ -1,6 +1,6 @@
 """GPU parity tests: the HIP engine vs the CPU oracle on identical inputs,
 including the reference's TPC-H golden vectors replayed from the committed
-fixture (no /root/reference on GPU boxes).
+fixture (no reference tree needed).
 
 Bars (north star): bit-exact COUNT/integer results; <= 1e-6 relative for
 double SUM/AVG (GPU tree-reduction order differs from the JVM loop's).

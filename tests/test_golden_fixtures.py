@@ -4,7 +4,7 @@ value equality.  These vectors are this build's byte-level pin for the column
 formats (the reference has no golden bytes — SURVEY.md §8(c)).
 
 Also replays TPC-H Q1/Q6 from the committed lineitem batch fixture, which is
-how GPU-box runs (no /root/reference) reproduce Snappy_1.out/Snappy_6.out.
+how runs without the reference tree reproduce Snappy_1.out/Snappy_6.out.
 """
 import json
 import os

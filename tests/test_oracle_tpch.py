@@ -1,27 +1,22 @@
 """Pin the CPU oracle against the reference's own TPC-H golden vectors.
 
-Golden source: /root/reference/tests/common/src/main/resources/TPCH/RESULT/
-Snappy_{1,6}.out computed from the bundled lineitem.tbl (30,201 rows),
+Golden source: the reference's tests/common/src/main/resources/TPCH/RESULT/
+Snappy_{1,6}.out computed from its bundled lineitem.tbl (30,201 rows),
 validated by the reference's TPCHDUnitTest.scala:57-71,643-713.
-These tests run in the build container where /root/reference exists; the
-expectations are also committed in tpch_util.GOLDEN_* so parity survives on
-boxes without the reference tree.
+The tests are self-contained: the lineitem rows come from the committed batch
+fixture tests/golden/lineitem_batches.bin (that same lineitem.tbl, encoded by
+tests/golden/make_fixtures.py) and the result lines from the copies under
+tests/golden/.
 """
-import os
-
 import pytest
 
 from tests import tpch_util as tu
 from oracle import pyoracle as po
 
-HAVE_REF = os.path.isdir(tu.REFERENCE_TPCH)
-
 
 @pytest.fixture(scope="module")
 def lineitem():
-    if not HAVE_REF:
-        pytest.skip("reference TPCH data not present on this box")
-    return tu.load_lineitem_tbl()
+    return tu.load_lineitem_fixture()
 
 
 @pytest.fixture(scope="module")
@@ -33,8 +28,6 @@ def oracle_table(lineitem):
 
 
 def test_golden_files_match_committed_copies():
-    if not HAVE_REF:
-        pytest.skip("reference tree absent")
     assert tu.load_golden(6) == tu.GOLDEN_Q6
     assert sorted(tu.load_golden(1)) == tu.GOLDEN_Q1
 

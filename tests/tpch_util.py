@@ -21,7 +21,7 @@ import os
 
 from oracle import pyoracle as po
 
-REFERENCE_TPCH = "/root/reference/tests/common/src/main/resources/TPCH"
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 LINEITEM_DTYPES = [po.T_DOUBLE, po.T_DOUBLE, po.T_DOUBLE, po.T_DOUBLE,
                    po.T_STRING, po.T_STRING, po.T_INT32]
@@ -34,10 +34,10 @@ def days(y, m, d):
     return (datetime.date(y, m, d) - EPOCH).days
 
 
-def load_lineitem_tbl(path=None):
-    """Parse the bundled lineitem.tbl into column lists (30,201 rows)."""
+def load_lineitem_tbl(path):
+    """Parse the reference's bundled lineitem.tbl (tests/common/src/main/
+    resources/TPCH/lineitem.tbl, 30,201 rows) into column lists."""
     import numpy as np
-    path = path or os.path.join(REFERENCE_TPCH, "lineitem.tbl")
     qty, ep, disc, tax, rf, ls, ship = [], [], [], [], [], [], []
     with open(path, "rb") as f:
         for line in f:
@@ -56,6 +56,28 @@ def load_lineitem_tbl(path=None):
         "qty": np.array(qty), "ep": np.array(ep), "disc": np.array(disc),
         "tax": np.array(tax), "rf": rf, "ls": ls,
         "ship": np.array(ship, dtype=np.int32),
+    }
+
+
+def load_lineitem_fixture():
+    """The same 30,201 lineitem rows, in file order, decoded from the
+    committed batch fixture tests/golden/lineitem_batches.bin (the bundled
+    lineitem.tbl encoded by tests/golden/make_fixtures.py)."""
+    import numpy as np
+    from tests.golden.make_fixtures import read_batches
+    parts = [[] for _ in LINEITEM_DTYPES]
+    for num_rows, blobs, _stats in read_batches(
+            os.path.join(GOLDEN_DIR, "lineitem_batches.bin")):
+        for c, blob in enumerate(blobs):
+            vals, valid = po.decode(LINEITEM_DTYPES[c], blob, num_rows)
+            assert valid.all()
+            parts[c].append(vals)
+    num = [np.concatenate(p) for p in parts[:4]]
+    return {
+        "qty": num[0], "ep": num[1], "disc": num[2], "tax": num[3],
+        "rf": [v for p in parts[COL_RF] for v in p],
+        "ls": [v for p in parts[COL_LS] for v in p],
+        "ship": np.concatenate(parts[COL_SHIP]).astype(np.int32),
     }
 
 
@@ -136,13 +158,14 @@ def fmt(v):
 
 
 def load_golden(qnum):
-    p = os.path.join(REFERENCE_TPCH, "RESULT", f"Snappy_{qnum}.out")
+    """Result lines of the reference's TPCH/RESULT/Snappy_<qnum>.out, as
+    committed under tests/golden/."""
+    p = os.path.join(GOLDEN_DIR, f"Snappy_{qnum}.out")
     with open(p) as f:
         return [line.strip() for line in f if line.strip()]
 
 
-# Committed copies of the reference's golden expectations for GPU-box runs
-# (where /root/reference does not exist).  Source:
+# The reference's golden expectations.  Source:
 # tests/common/src/main/resources/TPCH/RESULT/Snappy_6.out, Snappy_1.out.
 GOLDEN_Q6 = ["596503.1903"]
 GOLDEN_Q1 = [
