@@ -388,6 +388,85 @@ int32_t sn_query_partials_sharded(sn_query *q, int32_t world, void *dst);
 int32_t sn_query_merge(sn_query *q, const void *blocks, int64_t stride,
                        int32_t n_blocks);
 
+/* ---- exact DECIMAL aggregation (precision <= 18) ----
+ * The reference loads TPC-H measures as DECIMAL(15,2) and Catalyst returns
+ * SUM/AVG over them as exact decimals (Sum/Average over DecimalType in
+ * SnappyHashAggregateExec's generated accumulate code).  A decimal column of
+ * precision <= 18 is stored by the reference as an 8-byte long holding the
+ * unscaled value — the readLongDecimal/writeLongDecimal path of
+ * ColumnEncoding/Uncompressed (cited from memory of the reference tree; the
+ * variable-length binary decimals of precision > 18 stay unbuilt).  Here
+ * such a column is an SN_TYPE_INT64 column: every INT64 ingest path
+ * (uncompressed, RLE, nulls, delete masks, update deltas, sn_batch_put_raw)
+ * and the exact lo_i/hi_i and IN-list predicates apply unchanged, with
+ * literals given unscaled (`l_discount between 0.05 and 0.07` at scale 2 is
+ * 5..7).  sn_query_submit keeps accepting decimal-declared columns as plain
+ * INT64 columns on the double path.
+ *
+ *   sn_table_set_decimal
+ *       — attaches DecimalType(precision, scale) metadata to an INT64 column
+ *         (ColumnFormatRelation schema metadata).  1 <= precision <= 18,
+ *         0 <= scale <= precision; anything else, or a non-INT64 column, is
+ *         SN_ERR_BADARG.
+ *   sn_query_submit_dec / sn_query_result_dec
+ *       — the decimal twin of sn_query_submit/sn_query_result: the same
+ *         ColumnTableScan -> Filter -> SnappyHashAggregateExec pipeline with
+ *         DecimalType aggregation buffers.  `plan` supplies table, predicates
+ *         and group columns (plan->naggs must be 0, join_dim SN_JOIN_NONE);
+ *         every factor column must be decimal-declared.  Kinds: SUM, AVG,
+ *         COUNT_STAR, MIN, MAX (MIN/MAX take exactly one factor).  The result
+ *         scale is the sum of the factor scales; AVG adds 4 and rounds
+ *         HALF_UP (Spark: avg(decimal(p,s)) -> decimal(p+4,s+4)); COUNT has
+ *         scale 0.  Spark non-ANSI semantics: a row contributes iff every
+ *         referenced column is non-null; SUM/AVG/MIN/MAX of an empty or
+ *         all-null group are NULL; a group with any surviving row whose
+ *         |product| >= 10^38, or whose final |sum| >= 10^38, is NULL.
+ *         Rejected with SN_ERR_UNSUPPORTED: sparse-hash group keys, slot
+ *         counts beyond the LDS accumulator capacity, joins, and factors
+ *         whose |add| + |mul| * 10^precision can exceed int64.
+ *         sn_query_wait/_destroy/_kernel_ms/_num_groups/_result/_result_page
+ *         work on the handle (vals = nearest double of the exact value);
+ *         sn_query_used_jit is 0; sn_query_order_by, sn_query_partials* and
+ *         sn_query_merge return SN_ERR_UNSUPPORTED.
+ *   sn_dec_to_string / sn_dec_avg
+ *       — host-only helpers (no GPU needed): Decimal.toString and the
+ *         Average result expression's divide. */
+typedef struct {
+  int32_t col, _pad;
+  int64_t add, mul;      /* add + mul*col, unscaled, at col's scale */
+} sn_dec_factor;
+
+typedef struct {
+  int32_t kind, nfactors;
+  sn_dec_factor factors[SN_MAX_FACTORS];
+} sn_dec_agg;
+
+typedef struct {
+  uint64_t lo;           /* two's-complement i128: (hi << 64) | lo */
+  int64_t  hi;
+  int32_t  scale;
+  uint8_t  is_null, _pad[3];
+} sn_dec_val;
+
+int32_t   sn_table_set_decimal(sn_engine *e, int32_t table, int32_t col,
+                               int32_t precision, int32_t scale);
+sn_query *sn_query_submit_dec(sn_engine *e, const sn_plan *plan,
+                              int32_t naggs, const sn_dec_agg *aggs);
+/* exact value of aggregate `agg` in result row `row` (the row order of
+ * sn_query_result) */
+int32_t   sn_query_result_dec(sn_query *q, int64_t row, int32_t agg,
+                              sn_dec_val *out);
+/* "-123.4500": writes a NUL-terminated string, returns its length
+ * (SN_ERR_BADARG when cap is too small; NULL formats as "NULL") */
+int32_t   sn_dec_to_string(const sn_dec_val *v, char *buf, int32_t cap);
+/* sum / count at scale+4, rounded HALF_UP; NULL for a NULL sum, count <= 0
+ * or a quotient of 10^38 or more */
+int32_t   sn_dec_avg(const sn_dec_val *sum, int64_t count, sn_dec_val *out);
+/* status code of the calling thread's last failure (pairs with
+ * sn_last_error; lets callers of the pointer-returning submits tell
+ * SN_ERR_UNSUPPORTED from SN_ERR_BADARG) */
+int32_t   sn_last_error_code(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,62 @@ def make_plan(table=0, preds=(), group_cols=(), aggs=(), join=None):
     return p
 
 
+class SnDecFactor(C.Structure):
+    _fields_ = [("col", C.c_int32), ("_pad", C.c_int32),
+                ("add", C.c_int64), ("mul", C.c_int64)]
+
+
+class SnDecAgg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nfactors", C.c_int32),
+                ("factors", SnDecFactor * SN_MAX_FACTORS)]
+
+
+class SnDecVal(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64),
+                ("scale", C.c_int32), ("is_null", C.c_uint8),
+                ("_pad", C.c_uint8 * 3)]
+
+
+def dec_val(value, scale=0):
+    """SnDecVal from a Python int (None -> SQL NULL)."""
+    v = SnDecVal()
+    v.scale = scale
+    if value is None:
+        v.is_null = 1
+        return v
+    u = int(value) & ((1 << 128) - 1)
+    v.lo = u & ((1 << 64) - 1)
+    hi = u >> 64
+    v.hi = hi - (1 << 64) if hi >= (1 << 63) else hi
+    return v
+
+
+def dec_int(v):
+    """Python int of an SnDecVal (None for SQL NULL)."""
+    if v.is_null:
+        return None
+    return (int(v.hi) << 64) | int(v.lo)
+
+
+def make_dec_plan(table=0, preds=(), group_cols=(), aggs=()):
+    """Decimal twin of make_plan: returns (plan, agg_array) for
+    sn_query_submit_dec.  Same conventions, but the plan carries no
+    aggregates and factor add/mul are Python ints (unscaled, at the factor
+    column's scale)."""
+    p = make_plan(table=table, preds=preds, group_cols=group_cols, aggs=())
+    arr = (SnDecAgg * len(aggs))()
+    for i, (kind, factors) in enumerate(aggs):
+        ag = arr[i]
+        ag.kind = {"sum": AGG_SUM, "count": AGG_COUNT_STAR,
+                   "avg": AGG_AVG, "min": AGG_MIN, "max": AGG_MAX}[kind]
+        ag.nfactors = len(factors)
+        for j, (col, add, mul) in enumerate(factors):
+            ag.factors[j].col = col
+            ag.factors[j].add = int(add)
+            ag.factors[j].mul = int(mul)
+    return p, arr
+
+
 def result_rows(res):
     out = []
     for r in range(res.nrows):

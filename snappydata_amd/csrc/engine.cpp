@@ -55,13 +55,16 @@
 /* ------------------------------------------------------------------ */
 /* error reporting                                                     */
 static thread_local char g_err[512];
+static thread_local int g_err_code = SN_OK;
 static int fail(int code, const char *fmt, ...) {
   va_list ap; va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+  g_err_code = code;
   return code;
 }
 extern "C" const char *sn_last_error(void) { return g_err; }
+extern "C" int32_t sn_last_error_code(void) { return g_err_code; }
 extern "C" const char *sn_engine_arch(void) { return "gfx950"; }
 
 #define HIP_OR_FAIL(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
@@ -236,6 +239,9 @@ struct Table {
   /* last adequate sparse hash-table capacity (log2): later queries start
    * there instead of rediscovering it through grow-and-retry */
   int sparse_cap_hint = 0;
+  /* DecimalType(precision, scale) metadata of INT64 columns holding
+   * unscaled decimals (sn_table_set_decimal); precision 0 = not decimal */
+  std::vector<int8_t> dec_prec, dec_scale;
   int64_t total_rows = 0;
   std::mutex mu;
 };
@@ -1798,6 +1804,14 @@ struct GroupOut {
   double sums[SN_MAX_AGGS] = { 0 };
   double counts[SN_MAX_AGGS] = { 0 };
   double rowcount = 0;
+  int slot = 0;   /* dense accumulator slot (decimal queries look their
+                     exact values up by it after the key sort) */
+};
+
+/* decimal-query request threaded through the shared submit body */
+struct DecReq {
+  int32_t naggs;
+  const sn_dec_agg *aggs;
 };
 
 struct sn_query {
@@ -1846,6 +1860,13 @@ struct sn_query {
   bool merged = false;
   std::vector<GroupOut> final_groups;
   int status = SN_OK;
+  /* exact DECIMAL query state (sn_query_submit_dec) */
+  bool dec = false;
+  int dec_ndev = 0;                      /* deduped device aggregates */
+  int dec_map[SN_MAX_AGGS];              /* logical agg -> device agg (-1: COUNT(*)) */
+  int dec_scale_of[SN_MAX_AGGS];         /* result scale per logical agg */
+  unsigned long long *dec_out = nullptr; /* device [nslots][sn_dec_row_cells] */
+  std::vector<sn_dec_val> dec_vals;      /* host [nslots][plan.naggs] */
   ~sn_query() {
     if (e) { e->ev_release(ev_start); e->ev_release(ev_stop); ev_start = ev_stop = nullptr; }
     if (ev_start) (void)hipEventDestroy(ev_start);
@@ -1911,7 +1932,13 @@ static int ensure_sparse_ws(sn_engine *e, int cap_log2, int naggs1) {
   return SN_OK;
 }
 
-extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
+/* shared submit body.  dec == NULL is sn_query_submit; otherwise `plan`
+ * carries a double-typed image of the decimal aggregates (so column
+ * collection, slot derivation, descriptor build and stats skipping are the
+ * double path's own code) and the launch section routes to the exact
+ * decimal kernels. */
+static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
+                             const DecReq *dec) {
   if (!e || !plan) { fail(SN_ERR_BADARG, "null engine/plan"); return nullptr; }
   Table *t = get_table(e, plan->table);
   if (!t) { fail(SN_ERR_BADARG, "unknown table %d", plan->table); return nullptr; }
@@ -2093,6 +2120,13 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
                           (int64_t)std::max(caps[1], 1);
     q->sparse = col_sparse[0] || col_sparse[1] ||
                 (!any_string && dense_slots > SN_BIG_GROUP_CAP);
+    if (q->sparse && dec) {
+      fail(SN_ERR_UNSUPPORTED,
+           "decimal aggregation needs dense group slots (dictionary strings "
+           "or stats-dense int16/int32 keys); sparse-hash group keys are "
+           "not supported");
+      return nullptr;
+    }
     if (q->sparse) {
       if (any_string) {
         fail(SN_ERR_UNSUPPORTED,
@@ -2326,7 +2360,7 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
            * when they cannot, fail loudly rather than round silently.
            * (Affine/multi-factor expressions are double-typed in SQL —
            * the 1e-6 double budget applies, no gate.) */
-          if ((dp.i64_mask & (1u << da.c0)) && sa.kind == SN_AGG_SUM &&
+          if (!dec && (dp.i64_mask & (1u << da.c0)) && sa.kind == SN_AGG_SUM &&
               sa.nfactors == 1 && sa.factors[0].add == 0.0 &&
               sa.factors[0].mul == 1.0) {
             int gc = sa.factors[0].col;
@@ -2561,7 +2595,7 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
 
   /* upload + launch */
   size_t out_n = (size_t)q->nslots * q->out_stride;
-  if (!q->sparse) {
+  if (!q->sparse && !dec) {
     q->dev_out = (double *)e->arena.alloc(out_n * 8);
     if (!q->dev_out) { fail(SN_ERR_NOMEM, "out alloc"); return nullptr; }
     q->owned.push_back({ q->dev_out, out_n * 8 });
@@ -2623,6 +2657,98 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
     const bool grouped_mode = plan->ngroup > 0 || q->join_group;
     q->pac = (grouped_mode && (hit ? hit->pac != 0 : agg_nulls)) || q->mm;
     dp.pac = q->pac ? 1 : 0;
+  }
+  if (dec) {
+    /* ---- exact DECIMAL launch (k_dec_keyless / k_dec_grouped) ----
+     * canonical int64 factors, identical expressions deduped (Q1's sum/avg
+     * pairs share a device aggregate), COUNT(*) from the slot rowcount */
+    sn_dev_dec_plan ddp;
+    memset(&ddp, 0, sizeof(ddp));
+    int nd = 0;
+    for (int a = 0; a < dec->naggs; a++) {
+      const sn_dec_agg &sa = dec->aggs[a];
+      q->agg_map[a] = a;
+      if (sa.kind == SN_AGG_COUNT_STAR) { q->dec_map[a] = -1; continue; }
+      sn_dev_dec_agg da;
+      memset(&da, 0, sizeof(da));
+      da.op = sa.kind == SN_AGG_MIN ? 1 : sa.kind == SN_AGG_MAX ? 2 : 0;
+      da.nf = sa.nfactors;
+      for (int f = 0; f < 3; f++) {
+        if (f < sa.nfactors) {
+          da.c[f] = q->cslot_of_col[sa.factors[f].col];
+          da.add[f] = sa.factors[f].add;
+          da.mul[f] = sa.factors[f].mul;
+        } else {
+          da.c[f] = da.c[0]; da.add[f] = 1; da.mul[f] = 0;
+        }
+      }
+      int idx = -1;
+      for (int j = 0; j < nd; j++)
+        if (memcmp(&ddp.aggs[j], &da, sizeof(da)) == 0) { idx = j; break; }
+      if (idx < 0) { idx = nd; ddp.aggs[nd++] = da; }
+      q->dec_map[a] = idx;
+    }
+    ddp.naggs = nd;
+    q->dec_ndev = nd;
+    if (plan->ngroup == 0) q->nslots = 1;
+    if (plan->ngroup > 0 &&
+        q->nslots > sn_dec_max_slots(dp.nused, nd)) {
+      fail(SN_ERR_UNSUPPORTED,
+           "decimal group cardinality %d exceeds the %d-slot LDS accumulator "
+           "capacity for %d columns x %d aggregates",
+           q->nslots, sn_dec_max_slots(dp.nused, nd), dp.nused, nd);
+      return nullptr;
+    }
+    /* double view for sn_query_result: [sums naggs][counts naggs][rowcount] */
+    q->dec = true;
+    q->pac = true;
+    q->dev_naggs = plan->naggs;
+    q->na_t = plan->naggs;
+    q->out_stride = 2 * (size_t)plan->naggs + 1;
+    dp.nslots = q->nslots;
+    if (ntiles > 0) {
+      const size_t row_cells = (size_t)sn_dec_row_cells(nd);
+      const size_t outb = (size_t)q->nslots * row_cells * 8;
+      q->dec_out = (unsigned long long *)e->arena.alloc(outb);
+      if (!q->dec_out) { fail(SN_ERR_NOMEM, "decimal out alloc"); return nullptr; }
+      q->owned.push_back({ q->dec_out, outb });
+      const size_t planb = sizeof(dp) + sizeof(ddp);
+      uint8_t *plans_dev = (uint8_t *)e->arena.alloc(planb);
+      if (!plans_dev ||
+          hipMemcpy(plans_dev, &dp, sizeof(dp), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(plans_dev + sizeof(dp), &ddp, sizeof(ddp),
+                    hipMemcpyHostToDevice) != hipSuccess) {
+        fail(SN_ERR_NOMEM, "decimal plan upload"); return nullptr;
+      }
+      q->owned.push_back({ plans_dev, planb });
+      const size_t grid = (size_t)std::min<int32_t>(ntiles, SN_DEC_GRID_CAP);
+      const size_t need = grid * (size_t)q->nslots * row_cells * 8;
+      if (e->scratch_sz < need) {
+        e->scratch = (double *)e->arena.alloc(need);
+        e->scratch_sz = need;
+        if (!e->scratch) { e->scratch_sz = 0; fail(SN_ERR_NOMEM, "scratch alloc"); return nullptr; }
+      }
+      q->ev_start = e->ev_acquire();
+      q->ev_stop = e->ev_acquire();
+      if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
+      int rc = sn_launch_dec_scan(&dp, (const sn_dev_plan *)plans_dev, &ddp,
+                                  (const sn_dev_dec_plan *)(plans_dev + sizeof(dp)),
+                                  (const sn_dev_batch *)db_dev,
+                                  (const sn_dev_tile *)tl_dev, ntiles,
+                                  q->dec_out,
+                                  (unsigned long long *)e->scratch, e->stream);
+      if (q->ev_stop) (void)hipEventRecord(q->ev_stop, e->stream);
+      if (rc != 0) {
+        fail(SN_ERR_GENERIC, "decimal kernel launch: %s",
+             hipGetErrorString((hipError_t)rc));
+        return nullptr;
+      }
+    }
+    {
+      std::lock_guard<std::mutex> ga(e->aux_mu);
+      e->live_q.insert(q.get());
+    }
+    return q.release();
   }
   if (q->sparse && ntiles > 0) {
     /* ---- open-address hash-aggregate launch (k_grouped_hash) ----
@@ -2973,8 +3099,303 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
   return q.release();
 }
 
+extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
+  return submit_impl(e, plan, nullptr);
+}
+
+/* ================================================================== */
+/* exact DECIMAL aggregation: host side                                */
+
+typedef unsigned __int128 u128_t;
+typedef __int128 i128_t;
+static const u128_t DEC_1E38 =
+    ((u128_t)0x4B3B4CA85A86C47Aull << 64) | 0x098A224000000000ull;
+
+static sn_dec_val dec_null(int32_t scale) {
+  sn_dec_val v;
+  memset(&v, 0, sizeof(v));
+  v.scale = scale;
+  v.is_null = 1;
+  return v;
+}
+static sn_dec_val dec_make(i128_t x, int32_t scale) {
+  sn_dec_val v;
+  memset(&v, 0, sizeof(v));
+  v.lo = (uint64_t)(u128_t)x;
+  v.hi = (int64_t)(x >> 64);
+  v.scale = scale;
+  return v;
+}
+static i128_t dec_i128(const sn_dec_val &v) {
+  return (i128_t)(((u128_t)(uint64_t)v.hi << 64) | v.lo);
+}
+static double dec_to_double(const sn_dec_val &v) {
+  return (double)((long double)dec_i128(v) / powl(10.0L, (long double)v.scale));
+}
+
+extern "C" int32_t sn_dec_to_string(const sn_dec_val *v, char *buf,
+                                    int32_t cap) {
+  if (!v || !buf || cap <= 0 || v->scale < 0 || v->scale > 76)
+    return fail(SN_ERR_BADARG, "bad decimal/buffer");
+  std::string s;
+  if (v->is_null) {
+    s = "NULL";
+  } else {
+    const i128_t x = dec_i128(*v);
+    u128_t m = x < 0 ? (u128_t)0 - (u128_t)x : (u128_t)x;
+    std::string digits;
+    do {
+      digits.push_back((char)('0' + (int)(m % 10)));
+      m /= 10;
+    } while (m != 0);
+    while ((int32_t)digits.size() < v->scale + 1) digits.push_back('0');
+    std::reverse(digits.begin(), digits.end());
+    if (x < 0) s.push_back('-');
+    s.append(digits, 0, digits.size() - (size_t)v->scale);
+    if (v->scale > 0) {
+      s.push_back('.');
+      s.append(digits, digits.size() - (size_t)v->scale, (size_t)v->scale);
+    }
+  }
+  if ((int32_t)s.size() + 1 > cap)
+    return fail(SN_ERR_BADARG, "decimal string needs %zu bytes", s.size() + 1);
+  memcpy(buf, s.c_str(), s.size() + 1);
+  return (int32_t)s.size();
+}
+
+/* Average's result expression: sum / count at scale+4, HALF_UP (Spark:
+ * avg(decimal(p,s)) -> decimal(p+4,s+4)).  |sum| * 10^4 needs up to ~140
+ * bits: three 64-bit limbs long-divided by the 64-bit count. */
+extern "C" int32_t sn_dec_avg(const sn_dec_val *sum, int64_t count,
+                              sn_dec_val *out) {
+  if (!sum || !out) return fail(SN_ERR_BADARG, "null decimal");
+  const int32_t scale = sum->scale + 4;
+  if (sum->is_null || count <= 0) { *out = dec_null(scale); return SN_OK; }
+  const i128_t x = dec_i128(*sum);
+  const bool neg = x < 0;
+  const u128_t m = neg ? (u128_t)0 - (u128_t)x : (u128_t)x;
+  const u128_t lo = (u128_t)(uint64_t)m * 10000u;
+  const u128_t hi = (u128_t)(uint64_t)(m >> 64) * 10000u + (lo >> 64);
+  const uint64_t limb[3] = { (uint64_t)lo, (uint64_t)hi, (uint64_t)(hi >> 64) };
+  const uint64_t d = (uint64_t)count;
+  uint64_t qd[3];
+  uint64_t rem = 0;
+  for (int i = 2; i >= 0; i--) {
+    const u128_t cur = ((u128_t)rem << 64) | limb[i];
+    qd[i] = (uint64_t)(cur / d);
+    rem = (uint64_t)(cur % d);
+  }
+  u128_t qv = ((u128_t)qd[1] << 64) | qd[0];
+  bool over = qd[2] != 0;
+  if ((u128_t)rem * 2 >= (u128_t)d) {      /* HALF_UP on the magnitude */
+    qv += 1;
+    if (qv == 0) over = true;
+  }
+  if (over || qv >= DEC_1E38) { *out = dec_null(scale); return SN_OK; }
+  *out = dec_make(neg ? -(i128_t)qv : (i128_t)qv, scale);
+  return SN_OK;
+}
+
+extern "C" int32_t sn_table_set_decimal(sn_engine *e, int32_t table,
+                                        int32_t col, int32_t precision,
+                                        int32_t scale) {
+  if (!e) return fail(SN_ERR_BADARG, "null engine");
+  Table *t = get_table(e, table);
+  if (!t) return fail(SN_ERR_BADARG, "unknown table %d", table);
+  std::lock_guard<std::mutex> g(t->mu);
+  if (col < 0 || col >= (int32_t)t->schema.size())
+    return fail(SN_ERR_BADARG, "bad column %d", col);
+  if (t->schema[col].dtype != SN_TYPE_INT64)
+    return fail(SN_ERR_BADARG,
+                "decimal column %d must be INT64 (unscaled long decimal)", col);
+  if (precision < 1 || precision > 18)
+    return fail(SN_ERR_BADARG,
+                "decimal precision %d outside 1..18 (long-decimal range)",
+                precision);
+  if (scale < 0 || scale > precision)
+    return fail(SN_ERR_BADARG, "decimal scale %d outside 0..precision %d",
+                scale, precision);
+  t->dec_prec.resize(t->schema.size(), 0);
+  t->dec_scale.resize(t->schema.size(), 0);
+  t->dec_prec[col] = (int8_t)precision;
+  t->dec_scale[col] = (int8_t)scale;
+  return SN_OK;
+}
+
+extern "C" sn_query *sn_query_submit_dec(sn_engine *e, const sn_plan *plan,
+                                         int32_t naggs,
+                                         const sn_dec_agg *aggs) {
+  if (!e || !plan || !aggs) { fail(SN_ERR_BADARG, "null engine/plan/aggs"); return nullptr; }
+  Table *t = get_table(e, plan->table);
+  if (!t) { fail(SN_ERR_BADARG, "unknown table %d", plan->table); return nullptr; }
+  if (naggs <= 0 || naggs > SN_MAX_AGGS) {
+    fail(SN_ERR_BADARG, "decimal naggs %d outside 1..%d", naggs, SN_MAX_AGGS);
+    return nullptr;
+  }
+  if (plan->naggs != 0) {
+    fail(SN_ERR_BADARG,
+         "decimal submit takes its aggregates separately: plan->naggs must be 0");
+    return nullptr;
+  }
+  if (plan->join_dim != SN_JOIN_NONE) {
+    fail(SN_ERR_UNSUPPORTED, "decimal aggregation over a join is not supported");
+    return nullptr;
+  }
+  sn_plan sp = *plan;
+  sp.naggs = naggs;
+  int scales[SN_MAX_AGGS];
+  {
+    std::lock_guard<std::mutex> g(t->mu);
+    static const int64_t P10[19] = {
+      1ll, 10ll, 100ll, 1000ll, 10000ll, 100000ll, 1000000ll, 10000000ll,
+      100000000ll, 1000000000ll, 10000000000ll, 100000000000ll,
+      1000000000000ll, 10000000000000ll, 100000000000000ll,
+      1000000000000000ll, 10000000000000000ll, 100000000000000000ll,
+      1000000000000000000ll };
+    for (int a = 0; a < naggs; a++) {
+      const sn_dec_agg &sa = aggs[a];
+      sn_agg &da = sp.aggs[a];
+      memset(&da, 0, sizeof(da));
+      da.kind = sa.kind;
+      scales[a] = 0;
+      if (sa.kind == SN_AGG_COUNT_STAR) continue;
+      const bool mm = sa.kind == SN_AGG_MIN || sa.kind == SN_AGG_MAX;
+      if (sa.kind != SN_AGG_SUM && sa.kind != SN_AGG_AVG && !mm) {
+        fail(SN_ERR_BADARG, "decimal aggregate %d: unknown kind %d", a, sa.kind);
+        return nullptr;
+      }
+      if (sa.nfactors < 1 || sa.nfactors > SN_MAX_FACTORS ||
+          (mm && sa.nfactors != 1)) {
+        fail(SN_ERR_BADARG,
+             "decimal aggregate %d: %d factors (SUM/AVG take 1..%d, MIN/MAX "
+             "exactly 1)", a, sa.nfactors, SN_MAX_FACTORS);
+        return nullptr;
+      }
+      da.nfactors = sa.nfactors;
+      for (int f = 0; f < sa.nfactors; f++) {
+        const sn_dec_factor &fa = sa.factors[f];
+        if (fa.col < 0 || fa.col >= (int32_t)t->schema.size()) {
+          fail(SN_ERR_BADARG, "decimal aggregate %d: bad column %d", a, fa.col);
+          return nullptr;
+        }
+        const int prec = (size_t)fa.col < t->dec_prec.size()
+                             ? t->dec_prec[fa.col] : 0;
+        if (prec <= 0) {
+          fail(SN_ERR_BADARG,
+               "decimal aggregate %d: column %d is not declared decimal "
+               "(sn_table_set_decimal)", a, fa.col);
+          return nullptr;
+        }
+        /* factor values are formed in int64 on the device: prove
+         * |add| + |mul| * 10^precision cannot exceed it */
+        const i128_t aa = fa.add < 0 ? -(i128_t)fa.add : (i128_t)fa.add;
+        const i128_t am = fa.mul < 0 ? -(i128_t)fa.mul : (i128_t)fa.mul;
+        if (aa + am * (i128_t)P10[prec] > (i128_t)INT64_MAX) {
+          fail(SN_ERR_UNSUPPORTED,
+               "decimal aggregate %d factor %d: |add| + |mul| * 10^%d can "
+               "exceed int64", a, f, prec);
+          return nullptr;
+        }
+        scales[a] += t->dec_scale[fa.col];
+        da.factors[f].col = fa.col;
+        da.factors[f].add = (double)fa.add;
+        da.factors[f].mul = (double)fa.mul;
+      }
+      if (sa.kind == SN_AGG_AVG) scales[a] += 4;
+    }
+  }
+  DecReq req = { naggs, aggs };
+  sn_query *q = submit_impl(e, &sp, &req);
+  if (q) memcpy(q->dec_scale_of, scales, sizeof(int) * (size_t)naggs);
+  return q;
+}
+
+/* cells -> exact values (+ the double view sn_query_result reads) */
+static void dec_finalize(sn_query *q, const unsigned long long *cells) {
+  const sn_plan &p = q->plan;
+  const int nd = q->dec_ndev;
+  const size_t RC = (size_t)sn_dec_row_cells(nd);
+  q->dec_vals.assign((size_t)q->nslots * p.naggs, dec_null(0));
+  q->host_out.assign((size_t)q->nslots * q->out_stride, 0.0);
+  for (int s = 0; s < q->nslots; s++) {
+    const unsigned long long *row = cells ? cells + (size_t)s * RC : nullptr;
+    const unsigned long long rowcount = row ? row[RC - 1] : 0;
+    double *hrow = &q->host_out[(size_t)s * q->out_stride];
+    hrow[2 * p.naggs] = (double)rowcount;
+    for (int a = 0; a < p.naggs; a++) {
+      const int kind = p.aggs[a].kind;
+      const int scale = q->dec_scale_of[a];
+      sn_dec_val v = dec_null(scale);
+      unsigned long long cnt = 0;
+      if (kind == SN_AGG_COUNT_STAR) {
+        v = dec_make((i128_t)rowcount, 0);
+        cnt = rowcount;
+      } else if (row) {
+        const unsigned long long *c = row + (size_t)q->dec_map[a] * SN_DEC_CELLS;
+        cnt = c[3];
+        if (cnt > 0 && (kind == SN_AGG_MIN || kind == SN_AGG_MAX)) {
+          v = dec_make((i128_t)(int64_t)(c[0] ^ 0x8000000000000000ull), scale);
+        } else if (cnt > 0 && c[4] == 0) {
+          /* the 192-bit sum must fit i128 and stay below 10^38 */
+          const bool neg = (c[1] >> 63) != 0;
+          const bool fits = c[2] == (neg ? ~0ull : 0ull);
+          const i128_t x = (i128_t)(((u128_t)c[1] << 64) | c[0]);
+          const u128_t m = neg ? (u128_t)0 - (u128_t)x : (u128_t)x;
+          if (fits && m < DEC_1E38) {
+            const int sum_scale = kind == SN_AGG_AVG ? scale - 4 : scale;
+            v = dec_make(x, sum_scale);
+            if (kind == SN_AGG_AVG) {
+              sn_dec_val av;
+              (void)sn_dec_avg(&v, (int64_t)cnt, &av);
+              v = av;
+            }
+          }
+        }
+      }
+      q->dec_vals[(size_t)s * p.naggs + a] = v;
+      /* double view: result_fill_page divides AVG sums by counts, so a
+       * finished average travels as (value, 1); NULL as count 0 */
+      if (kind == SN_AGG_COUNT_STAR) {
+        hrow[a] = (double)rowcount;
+        hrow[p.naggs + a] = (double)rowcount;
+      } else if (!v.is_null) {
+        hrow[a] = dec_to_double(v);
+        hrow[p.naggs + a] = kind == SN_AGG_AVG ? 1.0 : (double)cnt;
+      }
+    }
+  }
+}
+
+extern "C" int32_t sn_query_result_dec(sn_query *q, int64_t row, int32_t agg,
+                                       sn_dec_val *out) {
+  if (!q || !out) return fail(SN_ERR_BADARG, "null query/out");
+  if (!q->dec) return fail(SN_ERR_BADARG, "not a decimal query");
+  int rc = sn_query_wait(q);
+  if (rc != SN_OK) return rc;
+  const int64_t n = sn_query_num_groups(q);
+  if (n < 0) return (int32_t)n;
+  if (row < 0 || row >= n || agg < 0 || agg >= q->plan.naggs)
+    return fail(SN_ERR_BADARG, "row/agg out of range");
+  const GroupOut &g = q->final_groups[(size_t)row];
+  *out = q->dec_vals[(size_t)g.slot * q->plan.naggs + agg];
+  return SN_OK;
+}
+
 extern "C" int32_t sn_query_wait(sn_query *q) {
   if (!q) return SN_ERR_BADARG;
+  if (!q->done && q->dec) {
+    HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
+    std::vector<unsigned long long> cells;
+    if (q->dec_out) {
+      cells.resize((size_t)q->nslots * sn_dec_row_cells(q->dec_ndev));
+      HIP_OR_FAIL(hipMemcpy(cells.data(), q->dec_out, cells.size() * 8,
+                            hipMemcpyDeviceToHost));
+    }
+    dec_finalize(q, q->dec_out ? cells.data() : nullptr);
+    if (q->ev_start && q->ev_stop)
+      (void)hipEventElapsedTime(&q->kernel_ms, q->ev_start, q->ev_stop);
+    q->done = true;
+  }
   if (!q->done) {
     HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
     size_t out_n = (size_t)q->nslots * q->out_stride;
@@ -3068,6 +3489,7 @@ static void local_groups(sn_query *q, std::vector<GroupOut> *out) {
     if ((p.ngroup > 0 || q->join_group) && rowcount == 0.0) continue;
     GroupOut g;
     g.rowcount = rowcount;
+    g.slot = s;
     for (int a = 0; a < p.naggs; a++) {
       if (p.ngroup == 0 && !q->join_group) {
         /* keyless MIN/MAX plans run the grouped (pac) layout with 1 slot:
@@ -3194,6 +3616,10 @@ extern "C" int32_t sn_query_result_page(sn_query *q, int64_t offset,
 extern "C" int32_t sn_query_order_by(sn_query *q, int32_t agg_idx,
                                      int32_t descending, int64_t k) {
   if (!q) return SN_ERR_BADARG;
+  if (q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_order_by is not supported on an exact decimal query (its "
+                "state is 128-bit fixed point, not the f64 partial layout)");
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
   if (q->final_groups.empty() && !q->merged) {
@@ -3287,17 +3713,29 @@ static int64_t partial_bytes_cap(sn_query *q, int32_t cap) {
 
 extern "C" int64_t sn_query_partial_bytes(sn_query *q) {
   if (!q) return SN_ERR_BADARG;
+  if (q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partial_bytes is not supported on an exact decimal query (its "
+                "state is 128-bit fixed point, not the f64 partial layout)");
   return partial_bytes_cap(q, SN_MAX_GROUP_SLOTS);
 }
 
 extern "C" int64_t sn_query_partial_bytes2(sn_query *q, int32_t cap_slots) {
   if (!q || cap_slots <= 0) return SN_ERR_BADARG;
+  if (q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partial_bytes2 is not supported on an exact decimal query (its "
+                "state is 128-bit fixed point, not the f64 partial layout)");
   return partial_bytes_cap(q, cap_slots);
 }
 
 extern "C" int32_t sn_query_partials2(sn_query *q, void *dst,
                                       int32_t dst_is_device, int32_t cap_slots) {
   if (!q || !dst || cap_slots <= 0) return SN_ERR_BADARG;
+  if (q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partials is not supported on an exact decimal query (its "
+                "state is 128-bit fixed point, not the f64 partial layout)");
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
   const sn_plan &p = q->plan;
@@ -3357,6 +3795,10 @@ extern "C" int32_t sn_query_partials_sharded2(sn_query *q, int32_t world,
                                               void *dst, int32_t cap_slots) {
   if (!q || !dst || world <= 0 || world > 1024 || cap_slots <= 0)
     return SN_ERR_BADARG;
+  if (q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partials_sharded is not supported on an exact decimal query (its "
+                "state is 128-bit fixed point, not the f64 partial layout)");
   const sn_plan &p = q->plan;
   if (p.ngroup == 0 && !q->join_group) return SN_ERR_UNSUPPORTED;
   int rc = sn_query_wait(q);
@@ -3407,6 +3849,10 @@ extern "C" int32_t sn_query_partials_sharded(sn_query *q, int32_t world,
 extern "C" int32_t sn_query_merge(sn_query *q, const void *blocks, int64_t stride,
                                   int32_t n_blocks) {
   if (!q || !blocks || n_blocks <= 0) return SN_ERR_BADARG;
+  if (q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_merge is not supported on an exact decimal query (its "
+                "state is 128-bit fixed point, not the f64 partial layout)");
   const sn_plan &p = q->plan;
   std::vector<GroupOut> merged;
   /* op-aware fold of one partial contribution into a GroupOut slot */

@@ -238,6 +238,70 @@ static inline int sn_grouped_needs_global(int nused, int nslots, int na1) {
   return lds > 160ull * 1024;
 }
 
+/* ---- exact DECIMAL aggregation (k_dec_keyless / k_dec_grouped) ----
+ * Canonical decimal aggregate input: value = f0*f1*f2 with
+ * f_i = add[i] + mul[i]*x_i formed in int64 (the host proves no int64 wrap
+ * from the declared precision) and the product formed in 128 bits.
+ * op: 0 = sum-accumulate (SUM/AVG), 1 = MIN, 2 = MAX (exactly one factor). */
+typedef struct {
+  int64_t add[3], mul[3];
+  int32_t c[3];
+  int32_t nf;
+  int32_t op;
+  int32_t _p;
+} sn_dev_dec_agg;
+
+typedef struct {
+  int32_t naggs, _p;
+  sn_dev_dec_agg aggs[12];
+} sn_dev_dec_plan;
+
+/* accumulator cells (u64) per aggregate:
+ *   [0..2] sum as a 192-bit two's-complement integer (lo, mid, hi limb) —
+ *          MIN/MAX keep the sign-biased value (v ^ 2^63) in cell 0
+ *   [3]    contributing (all-factors-non-null) row count
+ *   [4]    rows whose |product| reached 10^38 (group result becomes NULL)
+ * and one trailing surviving-row count per slot. */
+#define SN_DEC_CELLS 5
+#define SN_DEC_ROW_CELLS(naggs) ((naggs) * SN_DEC_CELLS + 1)   /* device-usable */
+static inline int sn_dec_row_cells(int naggs) {
+  return SN_DEC_ROW_CELLS(naggs);
+}
+/* LDS bytes of the decimal kernels: the shared decode front end's staging
+ * image (values, validity, dead/alive words), both plan mirrors, and the
+ * per-block accumulator of nslots rows (keyless: nslots == 1). */
+static inline unsigned long long sn_dec_lds_bytes(int nused, int nslots,
+                                                  int naggs) {
+  return (unsigned long long)nused * SN_SCAN_CHUNK * 8 +
+         (unsigned long long)nused * (SN_SCAN_CHUNK / 64) * 8 +
+         2ull * (SN_SCAN_CHUNK / 64) * 8 + 16 +
+         sizeof(sn_dev_plan) + sizeof(sn_dev_dec_plan) +
+         (unsigned long long)nslots * sn_dec_row_cells(naggs) * 8 +
+         4ull * sn_dec_row_cells(naggs) * 8 /* keyless per-wave partials */;
+}
+/* largest dense slot count the decimal grouped kernel admits (160 KiB LDS) */
+static inline int sn_dec_max_slots(int nused, int naggs) {
+  const unsigned long long fixed = sn_dec_lds_bytes(nused, 0, naggs);
+  if (fixed >= 160ull * 1024) return 0;
+  return (int)((160ull * 1024 - fixed) /
+               ((unsigned long long)sn_dec_row_cells(naggs) * 8));
+}
+/* replication factor of the grouped LDS accumulator (lane l updates copy
+ * l % copies, so few-group shapes do not serialize a whole wave on one LDS
+ * address): the largest power of two <= 16 that keeps a block within half
+ * the CU's LDS (two resident blocks), or within all of it when one copy
+ * already needs more than half. */
+static inline int sn_dec_copies(int nused, int nslots, int naggs) {
+  const unsigned long long budget =
+      sn_dec_lds_bytes(nused, nslots, naggs) <= 80ull * 1024 ? 80ull * 1024
+                                                             : 160ull * 1024;
+  int c = 1;
+  while (c < 16 && sn_dec_lds_bytes(nused, nslots * c * 2, naggs) <= budget)
+    c *= 2;
+  return c;
+}
+#define SN_DEC_GRID_CAP 512   /* blocks (scratch rows) of a decimal scan */
+
 #define SN_GRID_CAP 2048
 #define SN_RESULT_PAGE 1024      /* == SN_MAX_GROUP_SLOTS (result page) */
 #define SN_BIG_GROUP_CAP (1 << 20) /* dense-slot cap of the global-atomic
@@ -260,6 +324,18 @@ int sn_launch_scan_agg(const sn_dev_plan *plan,
                        double *dev_out,
                        double *dev_scratch,  /* >= min(ntiles,SN_GRID_CAP) x nv */
                        void *stream);
+
+/* exact decimal scan+filter+aggregate: block partials into dev_scratch
+ * (>= min(ntiles, SN_DEC_GRID_CAP) rows of nslots * sn_dec_row_cells u64),
+ * folded with carries into dev_out [nslots][sn_dec_row_cells].  plan->nslots
+ * <= 1 with ngroup == 0 runs the register-accumulator keyless kernel. */
+int sn_launch_dec_scan(const sn_dev_plan *plan, const sn_dev_plan *dev_plan,
+                       const sn_dev_dec_plan *dec,
+                       const sn_dev_dec_plan *dev_dec,
+                       const sn_dev_batch *dev_batches,
+                       const sn_dev_tile *dev_tiles, int32_t ntiles,
+                       unsigned long long *dev_out,
+                       unsigned long long *dev_scratch, void *stream);
 
 /* put-time patch materialization into a null-free fixed-width device body */
 int sn_launch_patch_apply(void *body, const int32_t *pos, const double *val,

@@ -2375,3 +2375,523 @@ extern "C" int sn_launch_scan_agg(const sn_dev_plan *plan,
   err = hipGetLastError();
   return (int)err;
 }
+
+/* ================= exact DECIMAL aggregation =================
+ * Fixed-point twin of the double aggregate path: a decimal column is an
+ * INT64 column of unscaled values (the reference's 8-byte long decimals of
+ * precision <= 18), so the decode front end above — convert_chunk,
+ * alive_init, pred_sweeps and the raw-bit i64 LDS image — is reused as is
+ * and deletes, deltas, nulls, RLE and stats skipping behave identically.
+ * Clean full chunks take the same staged (software-pipelined) conversion.
+ * Only the accumulate phase differs: factors are formed in int64, their
+ * product in 128 bits with overflow detection, and sums accumulate in a
+ * 192-bit two's-complement integer (three u64 limbs with carry) so no
+ * reachable row count can wrap.  Integer addition is associative: results
+ * are bit-identical across runs, grid sizes and atomic orderings.
+ * No 128-bit division happens on the device (AVG divides on the host). */
+typedef unsigned long long u64_t;
+typedef __int128 i128_t;
+typedef unsigned __int128 u128_t;
+
+#define DEC_1E38_HI 0x4B3B4CA85A86C47Aull
+#define DEC_1E38_LO 0x098A224000000000ull
+#define DEC_SIGN 0x8000000000000000ull
+
+/* (l2:l1:l0) += (p2:p1:p0), 192-bit add with carry */
+__device__ __forceinline__ void acc192_add(u64_t &l0, u64_t &l1, u64_t &l2,
+                                           u64_t p0, u64_t p1, u64_t p2) {
+  const u64_t s0 = l0 + p0;
+  const u64_t c0 = s0 < p0;
+  const u64_t t1 = l1 + p1;
+  u64_t c1 = t1 < p1;
+  const u64_t s1 = t1 + c0;
+  c1 += s1 < c0;              /* wraps only when t1 == ~0 and c0 == 1 */
+  l0 = s0; l1 = s1; l2 = l2 + p2 + c1;
+}
+
+/* factor i of row r: add + mul * x in int64 (wrap-free for values within
+ * the declared precision — proven by the host at submit) */
+__device__ __forceinline__ long long dec_factor(const sn_dev_dec_agg &A, int i,
+                                                const double *sval, int r) {
+  const long long x =
+      __double_as_longlong(sval[(size_t)A.c[i] * CHUNK + r]);
+  return (long long)((u64_t)A.add[i] + (u64_t)A.mul[i] * (u64_t)x);
+}
+
+/* product of the row's factors as a two's-complement i128 (p1:p0).
+ * Returns 1 when |product| >= 10^38 (or does not fit 128 bits): the row
+ * then poisons its group to NULL instead of contributing. */
+__device__ __forceinline__ int dec_product(const sn_dev_dec_agg &A,
+                                           const double *sval, int r,
+                                           u64_t *p0, u64_t *p1) {
+  const u128_t lim = ((u128_t)DEC_1E38_HI << 64) | DEC_1E38_LO;
+  const long long f0 = dec_factor(A, 0, sval, r);
+  i128_t p = f0;
+  if (A.nf >= 2) p = (i128_t)f0 * (i128_t)dec_factor(A, 1, sval, r);
+  int ovf;
+  if (A.nf >= 3) {
+    /* |p| <= 2^126 here; multiply magnitudes limb-wise so the 128-bit
+     * overflow is observable without a wider type */
+    const long long f2 = dec_factor(A, 2, sval, r);
+    const int neg = (p < 0) != (f2 < 0);
+    const u128_t a = p < 0 ? (u128_t)0 - (u128_t)p : (u128_t)p;
+    const u64_t b = f2 < 0 ? (u64_t)0 - (u64_t)f2 : (u64_t)f2;
+    const u128_t hi = (u128_t)(u64_t)(a >> 64) * b;
+    const u128_t lo = (u128_t)(u64_t)a * b;
+    const u128_t hs = hi << 64;
+    const u128_t m = hs + lo;
+    ovf = ((u64_t)(hi >> 64) != 0) | (m < hs) | (m >= lim);
+    p = neg ? (i128_t)((u128_t)0 - m) : (i128_t)m;
+  } else {
+    const u128_t a = p < 0 ? (u128_t)0 - (u128_t)p : (u128_t)p;
+    ovf = a >= lim;
+  }
+  *p0 = (u64_t)(u128_t)p;
+  *p1 = (u64_t)((u128_t)p >> 64);
+  return ovf;
+}
+
+/* alive word of row r restricted to rows whose factor columns are all
+ * non-null (Spark Sum/Average/Min/Max skip null inputs) */
+__device__ __forceinline__ uint64_t dec_valid_word(const sn_dev_dec_agg &A,
+                                                   uint64_t w, int clean,
+                                                   const uint64_t *svalid,
+                                                   int r) {
+  if (!clean) {
+    if (A.nf >= 1) w &= svalid[(size_t)A.c[0] * (CHUNK / 64) + (r >> 6)];
+    if (A.nf >= 2) w &= svalid[(size_t)A.c[1] * (CHUNK / 64) + (r >> 6)];
+    if (A.nf >= 3) w &= svalid[(size_t)A.c[2] * (CHUNK / 64) + (r >> 6)];
+  }
+  return w;
+}
+
+__device__ __forceinline__ u64_t dec_cell0_ident(int op) {
+  return op == 1 ? ~0ull : 0ull;   /* MIN starts at the top, MAX/SUM at 0 */
+}
+
+/* LDS carve-up shared by both decimal kernels (sn_dec_lds_bytes) */
+struct DecSmem {
+  double *sval;
+  uint64_t *svalid, *sdead, *salive;
+  sn_dev_plan *P;
+  sn_dev_dec_plan *D;
+  u64_t *bacc;
+};
+__device__ __forceinline__ DecSmem dec_smem(char *smem, int nused,
+                                            const sn_dev_plan *plan_g,
+                                            const sn_dev_dec_plan *dec_g) {
+  DecSmem s;
+  s.sval = (double *)smem;
+  s.svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
+  s.sdead = s.svalid + (size_t)nused * (CHUNK / 64);
+  s.salive = s.sdead + CHUNK / 64;
+  s.P = (sn_dev_plan *)(s.salive + CHUNK / 64 + 2);
+  s.D = (sn_dev_dec_plan *)(s.P + 1);
+  s.bacc = (u64_t *)(s.D + 1);
+  const int tid = threadIdx.x;
+  {
+    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
+    unsigned *dst = (unsigned *)s.P;
+    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
+  }
+  {
+    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)dec_g;
+    unsigned *dst = (unsigned *)s.D;
+    for (unsigned i = tid; i < sizeof(sn_dev_dec_plan) / 4; i += WG) dst[i] = src[i];
+  }
+  return s;
+}
+
+/* ---- keyless: per-lane register accumulators, reduced across the wave
+ * with add-with-carry, block partial rows to scratch with plain stores
+ * (the k_keyless -> k_reduce structure: same-address global atomics
+ * serialize, see k_keyless) ---- */
+template <int NA, int NC>
+__global__ __launch_bounds__(WG, 1)
+void k_dec_keyless(sn_dev_plan plan,
+                   const sn_dev_plan *__restrict__ plan_g,
+                   const sn_dev_dec_plan *__restrict__ dec_g,
+                   const sn_dev_batch *__restrict__ batches,
+                   const sn_dev_tile *__restrict__ tiles, int ntiles,
+                   u64_t *__restrict__ out) {
+  const int tid = threadIdx.x;
+  const int nused = plan.nused;
+  const int npd = plan.npreds_d, npi = plan.npreds_i;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const DecSmem S = dec_smem(smem, nused, plan_g, dec_g);
+  __syncthreads();
+  const int naggs = S.D->naggs;
+
+  u64_t l0[NA], l1[NA], l2[NA];
+  unsigned cnt[NA], ovf[NA];
+  unsigned rcnt = 0;
+#pragma unroll
+  for (int a = 0; a < NA; a++) {
+    l0[a] = a < naggs ? dec_cell0_ident(S.D->aggs[a].op) : 0ull;
+    l1[a] = 0; l2[a] = 0; cnt[a] = 0; ovf[a] = 0;
+  }
+
+  Stage<NC> st;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int num_rows = b.num_rows;
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
+    const int clean = b.clean;
+    ColRegs cr[NC];
+    hoist_cols(b, nused, cr);
+    const int pipe = batch_stageable(clean, nused, cr);
+    int staged = 0;
+    if (pipe && tile.row_start + CHUNK <= tile_end) {
+      stage_load(cr, nused, tile.row_start, st);
+      staged = 1;
+    }
+    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
+      const int rows = min(CHUNK, tile_end - base);
+      if (staged) stage_write(cr, nused, st, S.sval);
+      else convert_chunk(b, nused, base, rows, num_rows, S.sval, S.svalid, S.sdead);
+      __syncthreads();
+      /* prefetch the NEXT full chunk under this chunk's row phase */
+      const int nbase = base + CHUNK;
+      const int next_staged = pipe && nbase + CHUNK <= tile_end;
+      if (next_staged) stage_load(cr, nused, nbase, st);
+      alive_init(S.salive, S.sdead, rows, clean);
+      pred_sweeps(S.P, npd, npi, clean, S.sval, S.svalid, S.salive);
+#pragma unroll
+      for (int a = 0; a < NA; a++) {
+        if (a >= naggs) break;
+        const sn_dev_dec_agg A = S.D->aggs[a];
+#pragma unroll 2
+        for (int k = 0; k < CHUNK / WG; k++) {
+          const int r = tid + k * WG;
+          const uint64_t w =
+              dec_valid_word(A, S.salive[r >> 6], clean, S.svalid, r);
+          if (w == 0) continue;
+          if (!((w >> (tid & 63)) & 1ull)) continue;
+          cnt[a]++;
+          if (A.op == 0) {
+            u64_t p0, p1;
+            if (dec_product(A, S.sval, r, &p0, &p1)) ovf[a]++;
+            else acc192_add(l0[a], l1[a], l2[a], p0, p1,
+                            (p1 & DEC_SIGN) ? ~0ull : 0ull);
+          } else {
+            const u64_t v = (u64_t)dec_factor(A, 0, S.sval, r) ^ DEC_SIGN;
+            l0[a] = A.op == 1 ? (v < l0[a] ? v : l0[a]) : (v > l0[a] ? v : l0[a]);
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        const int r = tid + k * WG;
+        rcnt += (unsigned)((S.salive[r >> 6] >> (tid & 63)) & 1ull);
+      }
+      __syncthreads();
+      staged = next_staged;
+    }
+  }
+
+  /* wave reduction with carries, then the 4 wave partials fold in LDS */
+  const int RC = SN_DEC_ROW_CELLS(naggs);
+  u64_t *wpart = S.bacc + RC;              /* [WG/64][RC] */
+  const int wid = tid >> 6;
+#pragma unroll
+  for (int a = 0; a < NA; a++) {
+    if (a >= naggs) break;
+    const int op = S.D->aggs[a].op;
+    u64_t x0 = l0[a], x1 = l1[a], x2 = l2[a];
+    u64_t c = cnt[a], o = ovf[a];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const u64_t y0 = __shfl_down(x0, off, 64);
+      const u64_t y1 = __shfl_down(x1, off, 64);
+      const u64_t y2 = __shfl_down(x2, off, 64);
+      c += __shfl_down(c, off, 64);
+      o += __shfl_down(o, off, 64);
+      if (op == 0) acc192_add(x0, x1, x2, y0, y1, y2);
+      else if (op == 1) x0 = y0 < x0 ? y0 : x0;
+      else x0 = y0 > x0 ? y0 : x0;
+    }
+    if ((tid & 63) == 0) {
+      u64_t *cell = wpart + (size_t)wid * RC + a * SN_DEC_CELLS;
+      cell[0] = x0; cell[1] = x1; cell[2] = x2; cell[3] = c; cell[4] = o;
+    }
+  }
+  {
+    u64_t rc = rcnt;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) rc += __shfl_down(rc, off, 64);
+    if ((tid & 63) == 0) wpart[(size_t)wid * RC + RC - 1] = rc;
+  }
+  __syncthreads();
+  if (tid < naggs) {
+    const int op = S.D->aggs[tid].op;
+    const u64_t *c0 = wpart + tid * SN_DEC_CELLS;
+    u64_t x0 = c0[0], x1 = c0[1], x2 = c0[2], c = c0[3], o = c0[4];
+    for (int w = 1; w < WG / 64; w++) {
+      const u64_t *cw = c0 + (size_t)w * RC;
+      if (op == 0) acc192_add(x0, x1, x2, cw[0], cw[1], cw[2]);
+      else if (op == 1) x0 = cw[0] < x0 ? cw[0] : x0;
+      else x0 = cw[0] > x0 ? cw[0] : x0;
+      c += cw[3]; o += cw[4];
+    }
+    u64_t *dst = out + (size_t)blockIdx.x * RC + tid * SN_DEC_CELLS;
+    dst[0] = x0; dst[1] = x1; dst[2] = x2; dst[3] = c; dst[4] = o;
+  } else if (tid == 64) {
+    u64_t rc = 0;
+    for (int w = 0; w < WG / 64; w++) rc += wpart[(size_t)w * RC + RC - 1];
+    out[(size_t)blockIdx.x * RC + RC - 1] = rc;
+  }
+}
+
+/* ---- grouped: dense slots (dictionary ids / stats-dense integer keys, the
+ * slot derivation of k_grouped_lds) into a per-block LDS accumulator with
+ * 64-bit LDS atomics; each limb's carry comes from the atomic's returned
+ * old value, so the 192-bit sum is exact under any interleaving.  Limb
+ * atomics whose addend is zero are skipped (small positive products touch
+ * one limb).  Few-group shapes (Q1: 4 live groups) would serialize all 64
+ * lanes of a wave on the same LDS address, so the accumulator is replicated
+ * `copies` times (power of two, sn_dec_copies) and lane l updates copy
+ * l % copies; the copies fold with carries in the single per-block flush. ---- */
+template <int NC>
+__global__ __launch_bounds__(WG, 1)
+void k_dec_grouped(sn_dev_plan plan,
+                   const sn_dev_plan *__restrict__ plan_g,
+                   const sn_dev_dec_plan *__restrict__ dec_g,
+                   const sn_dev_batch *__restrict__ batches,
+                   const sn_dev_tile *__restrict__ tiles, int ntiles,
+                   u64_t *__restrict__ out, int copies) {
+  const int tid = threadIdx.x;
+  const int nused = plan.nused;
+  const int ngroup = plan.ngroup;
+  const int npd = plan.npreds_d, npi = plan.npreds_i;
+  const int nslots = plan.nslots;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const DecSmem S = dec_smem(smem, nused, plan_g, dec_g);
+  __syncthreads();
+  const int naggs = S.D->naggs;
+  const int RC = SN_DEC_ROW_CELLS(naggs);
+  const int NV = nslots * RC;
+  u64_t *bacc = S.bacc;
+  for (int i = tid; i < NV * copies; i += WG) {
+    const int ci = i % RC;
+    const int a = ci / SN_DEC_CELLS;
+    bacc[i] = (ci < RC - 1 && ci % SN_DEC_CELLS == 0)
+                  ? dec_cell0_ident(S.D->aggs[a].op) : 0ull;
+  }
+  __syncthreads();
+
+  const int gc0 = plan.gcol[0], gc1 = plan.gcol[1];
+  Stage<NC> st;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int num_rows = b.num_rows;
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
+    const int clean = b.clean;
+    ColRegs cr[NC];
+    hoist_cols(b, nused, cr);
+    const int pipe = batch_stageable(clean, nused, cr);
+    int staged = 0;
+    if (pipe && tile.row_start + CHUNK <= tile_end) {
+      stage_load(cr, nused, tile.row_start, st);
+      staged = 1;
+    }
+    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
+      const int rows = min(CHUNK, tile_end - base);
+      if (staged) stage_write(cr, nused, st, S.sval);
+      else convert_chunk(b, nused, base, rows, num_rows, S.sval, S.svalid, S.sdead);
+      __syncthreads();
+      /* prefetch the NEXT full chunk under this chunk's row phase */
+      const int nbase = base + CHUNK;
+      const int next_staged = pipe && nbase + CHUNK <= tile_end;
+      if (next_staged) stage_load(cr, nused, nbase, st);
+      alive_init(S.salive, S.sdead, rows, clean);
+      pred_sweeps(S.P, npd, npi, clean, S.sval, S.svalid, S.salive);
+      /* slot per row first (-1: dead), then aggregate-outer sweeps so each
+       * aggregate's parameters are read from the LDS plan mirror once per
+       * chunk, not once per row */
+      int slots[CHUNK / WG];
+      u64_t *const mybase = bacc + (size_t)(tid & (copies - 1)) * NV;
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        const int r = tid + k * WG;
+        const int alive = (int)((S.salive[r >> 6] >> (tid & 63)) & 1ull);
+        int slot = 0;
+        if (ngroup >= 1)
+          slot = (int)(((long long)S.sval[(size_t)gc0 * CHUNK + r] -
+                        S.P->gbase[0]) * S.P->gmul0);
+        if (ngroup >= 2)
+          slot += (int)((long long)S.sval[(size_t)gc1 * CHUNK + r] -
+                        S.P->gbase[1]);
+        /* (a live row's slot is in range by construction; the bound keeps
+         * a corrupt key from writing outside the accumulator) */
+        slots[k] = (alive && (unsigned)slot < (unsigned)nslots) ? slot : -1;
+        if (slots[k] >= 0)
+          (void)atomicAdd(&mybase[(size_t)slots[k] * RC + RC - 1], 1ull);
+      }
+      for (int a = 0; a < naggs; a++) {
+        const sn_dev_dec_agg A = S.D->aggs[a];
+#pragma unroll
+        for (int k = 0; k < CHUNK / WG; k++) {
+          if (slots[k] < 0) continue;
+          const int r = tid + k * WG;
+          if (!((dec_valid_word(A, ~0ull, clean, S.svalid, r) >> (tid & 63)) & 1ull))
+            continue;
+          u64_t *cell = mybase + (size_t)slots[k] * RC + a * SN_DEC_CELLS;
+          (void)atomicAdd(&cell[3], 1ull);
+          if (A.op == 0) {
+            u64_t p0, p1;
+            if (dec_product(A, S.sval, r, &p0, &p1)) {
+              (void)atomicAdd(&cell[4], 1ull);
+            } else {
+              const u64_t p2 = (p1 & DEC_SIGN) ? ~0ull : 0ull;
+              u64_t c0 = 0;
+              if (p0) {
+                const u64_t old0 = atomicAdd(&cell[0], p0);
+                c0 = (u64_t)(old0 + p0) < p0;
+              }
+              const u64_t a1 = p1 + c0;
+              u64_t c1 = a1 < c0;     /* wraps only when p1 == ~0, c0 == 1 */
+              if (a1) {
+                const u64_t old1 = atomicAdd(&cell[1], a1);
+                c1 += (u64_t)(old1 + a1) < a1;
+              }
+              const u64_t a2 = p2 + c1;
+              if (a2) (void)atomicAdd(&cell[2], a2);
+            }
+          } else {
+            const u64_t v = (u64_t)dec_factor(A, 0, S.sval, r) ^ DEC_SIGN;
+            if (A.op == 1) (void)atomicMin(&cell[0], v);
+            else (void)atomicMax(&cell[0], v);
+          }
+        }
+      }
+      __syncthreads();
+      staged = next_staged;
+    }
+  }
+  __syncthreads();
+  /* flush: one thread per (slot, aggregate | rowcount) folds the copies */
+  for (int i = tid; i < nslots * (naggs + 1); i += WG) {
+    const int slot = i / (naggs + 1), a = i % (naggs + 1);
+    u64_t *dst = out + (size_t)blockIdx.x * NV + (size_t)slot * RC;
+    if (a == naggs) {
+      u64_t rc = 0;
+      for (int c = 0; c < copies; c++)
+        rc += bacc[(size_t)c * NV + (size_t)slot * RC + RC - 1];
+      dst[RC - 1] = rc;
+      continue;
+    }
+    const int op = S.D->aggs[a].op;
+    u64_t x0 = dec_cell0_ident(op), x1 = 0, x2 = 0, cn = 0, ov = 0;
+    for (int c = 0; c < copies; c++) {
+      const u64_t *cell =
+          bacc + (size_t)c * NV + (size_t)slot * RC + a * SN_DEC_CELLS;
+      if (op == 0) acc192_add(x0, x1, x2, cell[0], cell[1], cell[2]);
+      else if (op == 1) x0 = cell[0] < x0 ? cell[0] : x0;
+      else x0 = cell[0] > x0 ? cell[0] : x0;
+      cn += cell[3]; ov += cell[4];
+    }
+    dst += a * SN_DEC_CELLS;
+    dst[0] = x0; dst[1] = x1; dst[2] = x2; dst[3] = cn; dst[4] = ov;
+  }
+}
+
+/* fold the per-block partial rows: one wave per (slot, aggregate) plus one
+ * per slot rowcount; lanes stride the blocks, then reduce with carries */
+__global__ __launch_bounds__(64)
+void k_dec_reduce(const u64_t *__restrict__ scratch, int nblocks, int nslots,
+                  const sn_dev_dec_plan *__restrict__ dec_g,
+                  u64_t *__restrict__ out) {
+  const GAS sn_dev_dec_plan *D = (const GAS sn_dev_dec_plan *)(uintptr_t)dec_g;
+  const GAS u64_t *src = (const GAS u64_t *)(uintptr_t)scratch;
+  const int naggs = D->naggs;
+  const int RC = SN_DEC_ROW_CELLS(naggs);
+  const size_t NV = (size_t)nslots * RC;
+  const int slot = blockIdx.x / (naggs + 1);
+  const int a = blockIdx.x % (naggs + 1);
+  if (slot >= nslots) return;
+  const int lane = threadIdx.x;
+  if (a == naggs) {
+    u64_t rc = 0;
+    for (int b = lane; b < nblocks; b += 64)
+      rc += src[(size_t)b * NV + (size_t)slot * RC + RC - 1];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) rc += __shfl_down(rc, off, 64);
+    if (lane == 0) out[(size_t)slot * RC + RC - 1] = rc;
+    return;
+  }
+  const int op = D->aggs[a].op;
+  u64_t x0 = dec_cell0_ident(op), x1 = 0, x2 = 0, c = 0, o = 0;
+  for (int b = lane; b < nblocks; b += 64) {
+    const GAS u64_t *cell =
+        src + (size_t)b * NV + (size_t)slot * RC + a * SN_DEC_CELLS;
+    const u64_t y0 = cell[0];
+    if (op == 0) acc192_add(x0, x1, x2, y0, cell[1], cell[2]);
+    else if (op == 1) x0 = y0 < x0 ? y0 : x0;
+    else x0 = y0 > x0 ? y0 : x0;
+    c += cell[3]; o += cell[4];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64_t y0 = __shfl_down(x0, off, 64);
+    const u64_t y1 = __shfl_down(x1, off, 64);
+    const u64_t y2 = __shfl_down(x2, off, 64);
+    c += __shfl_down(c, off, 64);
+    o += __shfl_down(o, off, 64);
+    if (op == 0) acc192_add(x0, x1, x2, y0, y1, y2);
+    else if (op == 1) x0 = y0 < x0 ? y0 : x0;
+    else x0 = y0 > x0 ? y0 : x0;
+  }
+  if (lane == 0) {
+    u64_t *dst = out + (size_t)slot * RC + a * SN_DEC_CELLS;
+    dst[0] = x0; dst[1] = x1; dst[2] = x2; dst[3] = c; dst[4] = o;
+  }
+}
+
+extern "C" int sn_launch_dec_scan(const sn_dev_plan *plan,
+                                  const sn_dev_plan *dev_plan,
+                                  const sn_dev_dec_plan *dec,
+                                  const sn_dev_dec_plan *dev_dec,
+                                  const sn_dev_batch *dev_batches,
+                                  const sn_dev_tile *dev_tiles, int32_t ntiles,
+                                  unsigned long long *dev_out,
+                                  unsigned long long *dev_scratch,
+                                  void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ntiles <= 0) return (int)hipErrorInvalidValue;
+  int grid;
+  if (ntiles <= SN_DEC_GRID_CAP) grid = ntiles;
+  else {
+    int rounds = (ntiles + SN_DEC_GRID_CAP - 1) / SN_DEC_GRID_CAP;
+    grid = (ntiles + rounds - 1) / rounds;
+  }
+  const int keyless = plan->ngroup == 0;
+  const int ns = keyless ? 1 : plan->nslots;
+  const int na = dec->naggs;
+  if (ns < 1 || na < 0 || na > 12) return (int)hipErrorInvalidValue;
+  if (sn_dec_lds_bytes(plan->nused, ns, na) > 160ull * 1024)
+    return (int)hipErrorInvalidValue;
+  const int copies = keyless ? 1 : sn_dec_copies(plan->nused, ns, na);
+  const size_t lds = (size_t)sn_dec_lds_bytes(plan->nused, ns * copies, na);
+  const bool nc4 = plan->nused <= 4;
+#define KDK(A, NCv) hipLaunchKernelGGL((k_dec_keyless<A, NCv>), dim3(grid), \
+        dim3(WG), lds, s, *plan, dev_plan, dev_dec, dev_batches, dev_tiles, \
+        ntiles, dev_scratch)
+#define KDG(NCv) hipLaunchKernelGGL((k_dec_grouped<NCv>), dim3(grid), \
+        dim3(WG), lds, s, *plan, dev_plan, dev_dec, dev_batches, dev_tiles, \
+        ntiles, dev_scratch, copies)
+  if (keyless) {
+    if (na <= 4) { if (nc4) KDK(4, 4); else KDK(4, 8); }
+    else { if (nc4) KDK(12, 4); else KDK(12, 8); }
+  } else {
+    if (nc4) KDG(4); else KDG(8);
+  }
+#undef KDK
+#undef KDG
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+  hipLaunchKernelGGL(k_dec_reduce, dim3(ns * (na + 1)), dim3(64), 0, s,
+                     dev_scratch, grid, ns, dev_dec, dev_out);
+  return (int)hipGetLastError();
+}

@@ -36,7 +36,10 @@ def build(force=False):
     """Compile the engine .so in-tree (hipcc --offload-arch=gfx950)."""
     srcdir = os.path.join(_DIR, "csrc")
     srcs = [os.path.join(srcdir, f) for f in
-            ("engine.cpp", "builder.cpp", "kernels.hip", "engine_internal.h")]
+            ("engine.cpp", "builder.cpp", "jit.cpp", "kernels.hip",
+             "engine_internal.h")]
+    srcs.append(os.path.join(os.path.dirname(_DIR), "include",
+                             "snappy_engine.h"))
     if force or (not os.path.exists(_SO)) or \
             os.path.getmtime(_SO) < max(os.path.getmtime(s) for s in srcs):
         subprocess.run(["make", "-C", srcdir], check=True)
@@ -142,6 +145,22 @@ def lib():
                                              C.POINTER(C.c_int32),
                                              C.POINTER(C.c_uint8), C.c_void_p,
                                              C.c_int64]
+        L.sn_last_error_code.restype = C.c_int32
+        L.sn_table_set_decimal.restype = C.c_int32
+        L.sn_table_set_decimal.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32]
+        L.sn_query_submit_dec.restype = C.c_void_p
+        L.sn_query_submit_dec.argtypes = [C.c_void_p, C.POINTER(abi.SnPlan),
+                                          C.c_int32, C.POINTER(abi.SnDecAgg)]
+        L.sn_query_result_dec.restype = C.c_int32
+        L.sn_query_result_dec.argtypes = [C.c_void_p, C.c_int64, C.c_int32,
+                                          C.POINTER(abi.SnDecVal)]
+        L.sn_dec_to_string.restype = C.c_int32
+        L.sn_dec_to_string.argtypes = [C.POINTER(abi.SnDecVal), C.c_char_p,
+                                       C.c_int32]
+        L.sn_dec_avg.restype = C.c_int32
+        L.sn_dec_avg.argtypes = [C.POINTER(abi.SnDecVal), C.c_int64,
+                                 C.POINTER(abi.SnDecVal)]
         L.sn_gen_lineitem_arrays.argtypes = [
             C.c_int64, C.c_int32, C.c_int64,
             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -201,6 +220,24 @@ def encode_update_delta(dtype, positions, num_base_rows, values, valid=None):
     return out[:n].tobytes()
 
 
+def dec_to_string(value, scale=0):
+    """Decimal.toString of an unscaled Python int (None -> 'NULL') through
+    the engine's host-side formatter; also accepts an abi.SnDecVal."""
+    v = value if isinstance(value, abi.SnDecVal) else abi.dec_val(value, scale)
+    buf = C.create_string_buffer(128)
+    _check(lib().sn_dec_to_string(C.byref(v), buf, len(buf)), "dec_to_string")
+    return buf.value.decode()
+
+
+def dec_avg(total, count, scale=0):
+    """sum / count at scale+4, HALF_UP (Spark's decimal average): returns
+    (python int or None, scale + 4)."""
+    v = abi.dec_val(total, scale)
+    out = abi.SnDecVal()
+    _check(lib().sn_dec_avg(C.byref(v), count, C.byref(out)), "dec_avg")
+    return abi.dec_int(out), out.scale
+
+
 def gen_lineitem_arrays(start_row, n, seed):
     """Generate the synthetic lineitem columns (same generator as the engine's
     sn_datagen_lineitem — used by tests and bench's CPU-baseline sample)."""
@@ -250,6 +287,24 @@ class Query:
                 break
             out.extend(abi.result_rows(res))
             off += res.nrows
+        return out
+
+    def dec_rows(self):
+        """Exact results of a decimal query (Engine.query_dec):
+        [(keys, [python int or None, ...], [scale, ...]), ...] in the row
+        order of rows(); each int is the unscaled value built from hi/lo."""
+        keyrows = self.rows()
+        naggs = len(self.dec_aggs)
+        out = []
+        v = abi.SnDecVal()
+        for r, (keys, _vals) in enumerate(keyrows):
+            ints, scales = [], []
+            for a in range(naggs):
+                _check(lib().sn_query_result_dec(self._h, r, a, C.byref(v)),
+                       "query_result_dec")
+                ints.append(abi.dec_int(v))
+                scales.append(int(v.scale))
+            out.append((keys, ints, scales))
         return out
 
     def kernel_ms(self):
@@ -481,6 +536,22 @@ class Engine:
         if not h:
             raise EngineError(-1, last_error())
         return Query(self, h, plan)
+
+    def table_set_decimal(self, table, col, precision, scale):
+        """Declare an INT64 column as DECIMAL(precision, scale) holding
+        unscaled values (precision <= 18, the reference's long decimals)."""
+        _check(lib().sn_table_set_decimal(self._h, table, col, precision,
+                                          scale), "table_set_decimal")
+
+    def query_dec(self, plan, aggs):
+        """Exact decimal aggregation: (plan, aggs) from abi.make_dec_plan.
+        Failures carry the engine's status code (e.g. SN_ERR_UNSUPPORTED)."""
+        h = lib().sn_query_submit_dec(self._h, C.byref(plan), len(aggs), aggs)
+        if not h:
+            raise EngineError(lib().sn_last_error_code(), last_error())
+        q = Query(self, h, plan)
+        q.dec_aggs = aggs
+        return q
 
     def close(self):
         if self._h:

@@ -1,0 +1,492 @@
+"""Exact DECIMAL aggregation on the GPU (sn_query_submit_dec): the reference
+everywhere is Python int arithmetic over the same rows, never the engine.
+
+Batch shapes are chosen against SN_SCAN_CHUNK=1024, SN_TILE_ROWS=16384 and
+the 256-lane workgroup: 17,445 rows = one full tile + one full chunk + a
+ragged 37-row tail; plus a 63-row batch (less than one wave) and a 1-row
+batch."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from snappydata_amd import abi, engine as se
+from tests import tpch_util as tu
+
+pytestmark = pytest.mark.gpu
+
+SN_ERR_UNSUPPORTED = -5
+SIZES = [17445, 17445, 17445, 63, 1]
+N = sum(SIZES)
+
+
+@pytest.fixture
+def eng():
+    e = se.Engine(device=0)
+    yield e
+    e.close()
+
+
+def half_up(v, s_from, s_to):
+    """Rescale an unscaled int from scale s_from to s_to, ROUND_HALF_UP."""
+    if v is None:
+        return None
+    if s_to >= s_from:
+        return v * 10 ** (s_to - s_from)
+    d = 10 ** (s_from - s_to)
+    q, r = divmod(abs(v), d)
+    if 2 * r >= d:
+        q += 1
+    return -q if v < 0 else q
+
+
+def py_avg(total, count, scale):
+    """Python-int reference of avg at scale+4, HALF_UP."""
+    if total is None or count == 0:
+        return None
+    q, r = divmod(abs(total) * 10 ** 4, count)
+    if 2 * r >= count:
+        q += 1
+    return -q if total < 0 else q
+
+
+def ingest(eng, table, cols, sizes):
+    """cols: per column either an ndarray or a list of bytes (strings);
+    one ingest call per batch so the batch sizes are exactly `sizes`."""
+    s = 0
+    for bi, n in enumerate(sizes):
+        part = []
+        for c in cols:
+            if isinstance(c, list):
+                vals = c[s:s + n]
+                part.append({"data": b"".join(vals),
+                             "lens": np.array([len(v) for v in vals],
+                                              dtype=np.int32)})
+            else:
+                part.append({"data": np.ascontiguousarray(c[s:s + n])})
+        assert eng.ingest_columns(table, part, n, batch_rows=n,
+                                  first_bucket=bi) == n
+        s += n
+    assert s == len(cols[0])
+
+
+def by_key(dec_rows):
+    return {keys: (vals, scales) for keys, vals, scales in dec_rows}
+
+
+# ---------------------------------------------------------------- 1. golden
+
+
+@pytest.fixture(scope="module")
+def lineitem_unscaled():
+    d = tu.load_lineitem_fixture()
+    out = {k: np.rint(d[k] * 100).astype(np.int64)
+           for k in ("qty", "ep", "disc", "tax")}
+    out["rf"], out["ls"], out["ship"] = d["rf"], d["ls"], d["ship"]
+    return out
+
+
+def load_lineitem(eng, d):
+    t = eng.table_define("li_dec", [(abi.T_INT64, False)] * 4 +
+                         [(abi.T_STRING, False)] * 2 + [(abi.T_INT32, False)])
+    n = len(d["qty"])
+    ingest(eng, t, [d["qty"], d["ep"], d["disc"], d["tax"], d["rf"], d["ls"],
+                    d["ship"]], [17445, n - 17445 - 64, 63, 1])
+    for c in range(4):
+        eng.table_set_decimal(t, c, 15, 2)
+    return t
+
+
+Q1_AGGS = [
+    ("sum", [(tu.COL_QTY, 0, 1)]),
+    ("sum", [(tu.COL_EP, 0, 1)]),
+    ("sum", [(tu.COL_EP, 0, 1), (tu.COL_DISC, 100, -1)]),
+    ("sum", [(tu.COL_EP, 0, 1), (tu.COL_DISC, 100, -1), (tu.COL_TAX, 100, 1)]),
+    ("avg", [(tu.COL_QTY, 0, 1)]),
+    ("avg", [(tu.COL_EP, 0, 1)]),
+    ("avg", [(tu.COL_DISC, 0, 1)]),
+    ("count", []),
+]
+
+
+def test_golden_q1(eng, lineitem_unscaled):
+    d = lineitem_unscaled
+    t = load_lineitem(eng, d)
+    cutoff = tu.days(1997, 12, 31) - 90
+    plan, aggs = abi.make_dec_plan(
+        table=t, preds=[dict(col=tu.COL_SHIP, hi=cutoff)],
+        group_cols=[tu.COL_RF, tu.COL_LS], aggs=Q1_AGGS)
+    q = eng.query_dec(plan, aggs)
+    rows = q.dec_rows()
+    assert not q.used_jit()
+    assert q.kernel_ms() > 0
+
+    # Python-int reference over the same rows
+    ref = {}
+    for i in np.nonzero(d["ship"] <= cutoff)[0]:
+        key = (d["rf"][i].decode(), d["ls"][i].decode())
+        qty, ep, disc, tax = (int(d[k][i]) for k in ("qty", "ep", "disc", "tax"))
+        a = ref.setdefault(key, [0, 0, 0, 0, 0, 0])
+        a[0] += qty
+        a[1] += ep
+        a[2] += ep * (100 - disc)
+        a[3] += ep * (100 - disc) * (100 + tax)
+        a[4] += disc
+        a[5] += 1
+    assert [k for k, _, _ in rows] == sorted(ref)
+    lines = []
+    for keys, vals, scales in rows:
+        r = ref[keys]
+        assert scales == [2, 2, 4, 6, 6, 6, 6, 0]
+        assert vals[3] == r[3]                      # raw scale-6 sum_charge
+        assert vals[:3] == r[:3]
+        assert vals[4] == py_avg(r[0], r[5], 2)
+        assert vals[5] == py_avg(r[1], r[5], 2)
+        assert vals[6] == py_avg(r[4], r[5], 2)
+        assert vals[7] == r[5]
+        parts = list(keys)
+        for a in range(7):
+            parts.append(se.dec_to_string(half_up(vals[a], scales[a], 4), 4))
+        parts.append(se.dec_to_string(vals[7], 0))
+        lines.append(",".join(parts))
+    assert lines == tu.load_golden(1)
+
+    # the double view of the same handle keeps Query.rows() working
+    for (keys, dvals), (_, vals, scales) in zip(q.rows(), rows):
+        for dv, v, s in zip(dvals, vals, scales):
+            assert abs(dv - v / 10 ** s) <= 1e-12 * max(1.0, abs(v / 10 ** s))
+
+
+def test_golden_q6(eng, lineitem_unscaled):
+    d = lineitem_unscaled
+    t = load_lineitem(eng, d)
+    lo, hi = tu.days(1994, 1, 1), tu.days(1995, 1, 1)
+    plan, aggs = abi.make_dec_plan(
+        table=t,
+        preds=[dict(col=tu.COL_SHIP, lo=lo, hi=hi, hi_strict=True),
+               dict(col=tu.COL_DISC, lo=5, hi=7),
+               dict(col=tu.COL_QTY, hi=2400, hi_strict=True)],
+        aggs=[("sum", [(tu.COL_EP, 0, 1), (tu.COL_DISC, 0, 1)]),
+              ("count", [])])
+    rows = eng.query_dec(plan, aggs).dec_rows()
+    m = ((d["ship"] >= lo) & (d["ship"] < hi) & (d["disc"] >= 5) &
+         (d["disc"] <= 7) & (d["qty"] < 2400))
+    exp = sum(int(e) * int(x) for e, x in zip(d["ep"][m], d["disc"][m]))
+    (keys, vals, scales), = rows
+    assert keys == () and scales == [4, 0]
+    assert vals == [exp, int(m.sum())] and m.sum() > 0
+    assert [se.dec_to_string(half_up(vals[0], 4, 4), 4)] == tu.load_golden(6)
+
+
+# --------------------------------------------------------------- 2. carries
+
+
+@pytest.fixture(scope="module")
+def carry_data():
+    rng = np.random.default_rng(116)
+    def col():
+        mag = (1 << 50) + rng.integers(0, 1 << 20, N)
+        sign = np.where(rng.random(N) < 0.25, -1, 1)
+        return (mag * sign).astype(np.int64)
+    return col(), col(), rng.integers(0, 8, N).astype(np.int32)
+
+
+def load_carry(eng, data):
+    a, b, k = data
+    t = eng.table_define("carry", [(abi.T_INT64, False), (abi.T_INT64, False),
+                                   (abi.T_INT32, False)])
+    ingest(eng, t, [a, b, k], SIZES)
+    eng.table_set_decimal(t, 0, 16, 3)
+    eng.table_set_decimal(t, 1, 16, 3)
+    return t
+
+
+CARRY_AGGS = [("sum", [(0, 0, 1), (1, 0, 1)]), ("sum", [(0, 7, -3)]),
+              ("min", [(0, 0, 1)]), ("max", [(1, 5, 2)]), ("count", [])]
+
+
+def carry_ref(a, b):
+    pa, pb = [int(x) for x in a], [int(x) for x in b]
+    return [sum(x * y for x, y in zip(pa, pb)), sum(7 - 3 * x for x in pa),
+            min(pa), max(5 + 2 * y for y in pb), len(pa)]
+
+
+def test_carries_keyless(eng, carry_data):
+    a, b, k = carry_data
+    t = load_carry(eng, carry_data)
+    plan, aggs = abi.make_dec_plan(table=t, aggs=CARRY_AGGS)
+    (keys, vals, scales), = eng.query_dec(plan, aggs).dec_rows()
+    exp = carry_ref(a, b)
+    assert vals == exp
+    assert scales == [6, 3, 3, 3, 0]
+    assert abs(exp[0]) > 1 << 110          # far beyond int64 and the f64 mantissa
+    # why the feature exists: the double path cannot hold this sum
+    drows = eng.query(abi.make_plan(
+        table=t, aggs=[("sum", [(0, 0.0, 1.0), (1, 0.0, 1.0)])])).rows()
+    assert int(drows[0][1][0]) != exp[0]
+    assert abs(drows[0][1][0] - exp[0]) <= 1e-9 * abs(exp[0])
+
+
+def test_carries_grouped(eng, carry_data):
+    a, b, k = carry_data
+    t = load_carry(eng, carry_data)
+    plan, aggs = abi.make_dec_plan(table=t, group_cols=[2], aggs=CARRY_AGGS)
+    rows = by_key(eng.query_dec(plan, aggs).dec_rows())
+    assert len(rows) == 8
+    drows = dict(eng.query(abi.make_plan(
+        table=t, group_cols=[2],
+        aggs=[("sum", [(0, 0.0, 1.0), (1, 0.0, 1.0)])])).rows())
+    for g in range(8):
+        m = k == g
+        exp = carry_ref(a[m], b[m])
+        assert rows[(str(g),)][0] == exp, g
+        assert int(drows[(str(g),)][0]) != exp[0]
+
+
+# -------------------------------------------------------------- 3. overflow
+
+
+def test_overflow(eng):
+    rng = np.random.default_rng(38)
+    n = N
+    x, y, z = (rng.integers(-999, 1000, n).astype(np.int64) for _ in range(3))
+    k = rng.integers(0, 8, n).astype(np.int32)
+    flag = np.zeros(n, dtype=np.int32)
+    big = 17000                      # inside the first batch's second tile
+    x[big] = y[big] = z[big] = 10 ** 17
+    k[big] = 3
+    flag[big] = 1
+    twenty = np.arange(20) * 2600 + 11   # spread over the batches
+    x[twenty], y[twenty], z[twenty] = 9 * 10 ** 17, 10 ** 17, 1000
+    k[twenty] = 5
+    flag[twenty] = 2
+    t = eng.table_define("ovf", [(abi.T_INT64, False)] * 3 +
+                         [(abi.T_INT32, False)] * 2)
+    ingest(eng, t, [x, y, z, k, flag], SIZES)
+    for c in range(3):
+        eng.table_set_decimal(t, c, 18, 0)
+    aggs_spec = [("sum", [(0, 0, 1), (1, 0, 1), (2, 0, 1)]), ("count", []),
+                 ("sum", [(0, 0, 1)])]
+
+    def ref(mask):
+        return sum(int(a) * int(b) * int(c)
+                   for a, b, c in zip(x[mask], y[mask], z[mask]))
+
+    # grouped, no predicate: group 3 holds the 10^51 row, group 5 the twenty
+    # 9*10^37 rows (each below 10^38, their sum 1.8*10^39 beyond even i128)
+    plan, aggs = abi.make_dec_plan(table=t, group_cols=[3], aggs=aggs_spec)
+    rows = by_key(eng.query_dec(plan, aggs).dec_rows())
+    for g in range(8):
+        vals = rows[(str(g),)][0]
+        m = k == g
+        assert vals[1] == int(m.sum())
+        assert vals[2] == int(x[m].astype(object).sum())
+        if g in (3, 5):
+            assert vals[0] is None, g
+        else:
+            assert vals[0] == ref(m), g
+    assert 9 * 10 ** 37 < 10 ** 38 <= 20 * 9 * 10 ** 37
+
+    # the same rows filtered out by a predicate: every group exact again
+    plan, aggs = abi.make_dec_plan(table=t, preds=[dict(col=4, hi=0)],
+                                   group_cols=[3], aggs=aggs_spec)
+    rows = by_key(eng.query_dec(plan, aggs).dec_rows())
+    for g in range(8):
+        m = (k == g) & (flag == 0)
+        assert rows[(str(g),)][0] == [ref(m), int(m.sum()),
+                                      int(x[m].astype(object).sum())]
+
+    # keyless: per-row overflow, end-of-sum overflow, and neither
+    for pred, null in [([dict(col=4, hi=1)], True),
+                       ([dict(col=4, **{"in": [0, 2]})], True),
+                       ([dict(col=4, hi=0)], False)]:
+        plan, aggs = abi.make_dec_plan(table=t, preds=pred, aggs=aggs_spec)
+        (_, vals, _), = eng.query_dec(plan, aggs).dec_rows()
+        if "in" in pred[0]:
+            m = (flag == 0) | (flag == 2)
+        else:
+            m = flag <= pred[0]["hi"]
+        assert vals[1] == int(m.sum())
+        assert vals[0] == (None if null else ref(m))
+
+
+# ---------------------------------------------------- 4. mutation and nulls
+
+
+def test_mutation_and_nulls(eng):
+    rng = np.random.default_rng(44)
+    sizes = [17445, 63, 1]
+    n = sum(sizes)
+    a = rng.integers(-10 ** 14, 10 ** 14, n).astype(np.int64)
+    a_valid = (rng.random(n) > 0.2)
+    b = np.repeat(rng.integers(-10 ** 6, 10 ** 6, n // 4),
+                  rng.integers(1, 14, n // 4))[:n].astype(np.int64)
+    assert len(b) == n
+    g = [(b"A", b"B", b"C")[i] for i in rng.integers(0, 3, n)]
+    for i in range(0, n, 97):          # group Z: every `a` is NULL
+        g[i] = b"Z"
+        a_valid[i] = False
+    t = eng.table_define("mut", [(abi.T_INT64, True), (abi.T_INT64, False),
+                                 (abi.T_STRING, False)])
+    eng.table_set_decimal(t, 0, 15, 2)
+    eng.table_set_decimal(t, 1, 15, 2)
+    av = [int(v) if ok else None for v, ok in zip(a, a_valid)]
+    bv = [int(v) for v in b]
+    alive = [True] * n
+    s = 0
+    for bi, nb in enumerate(sizes):
+        cols = [po.encode(po.T_INT64, po.ENC_UNCOMPRESSED, a[s:s + nb],
+                          valid=a_valid[s:s + nb].astype(np.uint8)),
+                po.encode(po.T_INT64, po.ENC_RLE, b[s:s + nb]),
+                po.encode(po.T_STRING, po.ENC_DICT, g[s:s + nb])]
+        eng.batch_put(t, bi, bi, nb, cols)
+        s += nb
+
+    spec = [("sum", [(0, 0, 1)]), ("sum", [(0, 0, 1), (1, 100, -1)]),
+            ("min", [(0, 0, 1)]), ("max", [(0, 0, 1)]), ("avg", [(0, 0, 1)]),
+            ("min", [(1, 0, 1)]), ("max", [(1, 0, 1)]), ("sum", [(1, 0, 1)]),
+            ("count", [])]
+
+    def ref(rows):
+        xs = [(av[i], bv[i]) for i in rows if alive[i]]
+        nn = [(p, q) for p, q in xs if p is not None]
+        sa = sum(p for p, _ in nn) if nn else None
+        return [sa,
+                sum(p * (100 - q) for p, q in nn) if nn else None,
+                min(p for p, _ in nn) if nn else None,
+                max(p for p, _ in nn) if nn else None,
+                py_avg(sa, len(nn), 2),
+                min(q for _, q in xs) if xs else None,
+                max(q for _, q in xs) if xs else None,
+                sum(q for _, q in xs) if xs else None,
+                len(xs)]
+
+    def check():
+        plan, aggs = abi.make_dec_plan(table=t, group_cols=[2], aggs=spec)
+        rows = by_key(eng.query_dec(plan, aggs).dec_rows())
+        groups = {}
+        for i in range(n):
+            if alive[i]:
+                groups.setdefault((g[i].decode(),), []).append(i)
+        assert set(rows) == set(groups)
+        for key, idx in groups.items():
+            assert rows[key][0] == ref(idx), key
+            assert rows[key][1] == [2, 4, 2, 2, 6, 2, 2, 2, 0]
+        z = rows[("Z",)][0]
+        assert z[:5] == [None] * 5 and z[8] == len(groups[("Z",)]) > 0
+        plan, aggs = abi.make_dec_plan(table=t, aggs=spec)
+        (_, vals, _), = eng.query_dec(plan, aggs).dec_rows()
+        assert vals == ref(range(n))
+
+    check()                              # nulls + RLE, clean of mutations
+
+    # delete mask + 2-deep update delta on the first (big) batch:
+    # delta1 overrides delta2 overrides base; some patches write NULL
+    nb = sizes[0]
+    dels = np.unique(rng.integers(0, nb, 900)).astype(np.int32)
+    # (group Z rows, every 97th, stay unpatched so the group stays all-NULL)
+    pos2 = np.unique(rng.integers(0, nb, 700)).astype(np.int32)
+    pos2 = pos2[pos2 % 97 != 0]
+    val2 = rng.integers(-10 ** 14, 10 ** 14, len(pos2)).astype(np.int64)
+    ok2 = rng.random(len(pos2)) > 0.1
+    pos1 = np.unique(np.concatenate([pos2[::3],
+                                     rng.integers(0, nb, 300)])).astype(np.int32)
+    pos1 = pos1[pos1 % 97 != 0]
+    val1 = rng.integers(-10 ** 14, 10 ** 14, len(pos1)).astype(np.int64)
+    ok1 = rng.random(len(pos1)) > 0.1
+    d2 = se.encode_update_delta(abi.T_INT64, pos2, nb, val2,
+                                valid=ok2.astype(np.uint8))
+    d1 = se.encode_update_delta(abi.T_INT64, pos1, nb, val1,
+                                valid=ok1.astype(np.uint8))
+    eng.batch_mutate(t, 0, 0, delete_mask=se.encode_delete_mask(dels, nb),
+                     deltas=[(d1, d2), (None, None), (None, None)])
+    for p, v, ok in zip(pos2, val2, ok2):
+        av[p] = int(v) if ok else None
+    for p, v, ok in zip(pos1, val1, ok1):
+        av[p] = int(v) if ok else None
+    for p in dels:
+        alive[p] = False
+    check()
+
+    # empty result: SUM/MIN/MAX/AVG NULL, COUNT 0; grouped: no rows
+    pred = [dict(col=1, lo=10 ** 9)]
+    plan, aggs = abi.make_dec_plan(table=t, preds=pred, aggs=spec)
+    (_, vals, _), = eng.query_dec(plan, aggs).dec_rows()
+    assert vals == [None] * 8 + [0]
+    plan, aggs = abi.make_dec_plan(table=t, preds=pred, group_cols=[2],
+                                   aggs=spec)
+    assert eng.query_dec(plan, aggs).dec_rows() == []
+
+
+# ----------------------------------------------------------- 5. determinism
+
+
+def test_determinism(eng, carry_data):
+    a, b, k = carry_data
+    t = load_carry(eng, carry_data)
+    # the same rows under a different batch split (another grid size)
+    t2 = eng.table_define("carry2", [(abi.T_INT64, False), (abi.T_INT64, False),
+                                     (abi.T_INT32, False)])
+    ingest(eng, t2, [a, b, k], [5000] * (N // 5000) + [N % 5000])
+    eng.table_set_decimal(t2, 0, 16, 3)
+    eng.table_set_decimal(t2, 1, 16, 3)
+    for group_cols in ([], [2]):
+        runs = []
+        for table in (t, t, t2):
+            plan, aggs = abi.make_dec_plan(table=table, group_cols=group_cols,
+                                           aggs=CARRY_AGGS)
+            q = eng.query_dec(plan, aggs)
+            nrows = q.num_groups()
+            bits = []
+            v = abi.SnDecVal()
+            for r in range(nrows):
+                for ai in range(len(CARRY_AGGS)):
+                    assert se.lib().sn_query_result_dec(q._h, r, ai,
+                                                        C.byref(v)) == 0
+                    bits.append((v.hi, v.lo, v.scale, v.is_null))
+            runs.append(bits)
+        assert runs[0] == runs[1] == runs[2]
+        assert len(runs[0]) == len(CARRY_AGGS) * (8 if group_cols else 1)
+
+
+# ---------------------------------------------------------- 6. loud rejects
+
+
+def test_loud_rejects(eng):
+    rng = np.random.default_rng(6)
+    n = 5000
+    v = rng.integers(-10 ** 6, 10 ** 6, n).astype(np.int64)
+    key64 = rng.integers(0, 1 << 40, n).astype(np.int64)
+    small = rng.integers(0, 4, n).astype(np.int32)
+    t = eng.table_define("rej", [(abi.T_INT64, False), (abi.T_INT64, False),
+                                 (abi.T_INT32, False)])
+    ingest(eng, t, [v, key64, small], [n])
+    eng.table_set_decimal(t, 0, 15, 2)
+    spec = [("sum", [(0, 0, 1)]), ("count", [])]
+    # sparse (hash-aggregate) group key
+    plan, aggs = abi.make_dec_plan(table=t, group_cols=[1], aggs=spec)
+    with pytest.raises(se.EngineError) as ei:
+        eng.query_dec(plan, aggs)
+    assert ei.value.code == SN_ERR_UNSUPPORTED and se.last_error()
+    # epilogues/exchange of the f64 layout do not apply to a decimal query
+    plan, aggs = abi.make_dec_plan(table=t, group_cols=[2], aggs=spec)
+    q = eng.query_dec(plan, aggs)
+    for call in (lambda: q.order_by(0),
+                 lambda: q.partials_host(),
+                 lambda: q.partials_host(cap=16),
+                 lambda: q.partials_sharded(2),
+                 lambda: q.merge_host(np.zeros(64, dtype=np.uint8), 64, 1)):
+        with pytest.raises(se.EngineError) as ei:
+            call()
+        assert ei.value.code == SN_ERR_UNSUPPORTED
+        assert se.last_error()
+    # the query itself is still good, and exact
+    rows = by_key(q.dec_rows())
+    for gk in range(4):
+        assert rows[(str(gk),)][0] == [int(v[small == gk].sum()),
+                                       int((small == gk).sum())]
+    # the double path keeps accepting the decimal-declared column
+    drows = eng.query(abi.make_plan(table=t, aggs=[("sum", [(0, 0.0, 1.0)]),
+                                                   ("count", [])])).rows()
+    assert drows[0][1] == [float(v.sum()), float(n)]
