@@ -85,10 +85,11 @@ typedef struct { int32_t batch; int32_t row_start; } sn_dev_tile;
 typedef struct { double lo, hi; int32_t cslot; int32_t _p; } sn_dev_pred_d;
 typedef struct { int64_t lo, hi; int32_t cslot; int32_t _p; } sn_dev_pred_i;
 
-/* Canonical aggregate input: value = (a0+m0*x0)*(a1+m1*x1)*(a2+m2*x2) with
- * unused factors neutralized to (1 + 0*x_c0) — three fmas, no branches.
- * COUNT(*) is all-neutral (value 1).  nf/c-slots retained for the general
- * path's per-factor null checks.  op: 0 = sum-accumulate (SUM/AVG/COUNT),
+/* Canonical aggregate input: value = (a0+m0*x0)*(a1+m1*x1)*(a2+m2*x2) over
+ * the first nf factors; the unused ones carry (a=1, m=0, c=c0) but are never
+ * evaluated (0*x is NaN for a NaN or infinite x).  COUNT(*) has nf == 0 and
+ * value 1.  nf also drives the general path's per-factor null checks.
+ * op: 0 = sum-accumulate (SUM/AVG/COUNT),
  * 1 = MIN, 2 = MAX — min/max accumulators store the ORDER-PRESERVING u64
  * encoding (sn_f64_ord) so device atomics are integer atomicMin/Max;
  * k_reduce (dense) or the host (sparse readback) decodes. */

@@ -495,13 +495,19 @@ __device__ __forceinline__ double sv_agg(const sn_dev_plan *P,
   return ((P->i64_mask >> cs) & 1u) ? xc : x;
 }
 
-/* aggregate input value: three neutral-padded fmas */
+/* aggregate input value: the product of the REAL factors only (A.nf is
+ * wave-uniform, so these are scalar branches).  A neutral factor must not be
+ * evaluated as (1 + 0*x): 0*x is NaN when x is NaN or +-inf, and COUNT(*)
+ * (nf == 0) of a plan that references no column has no staged slot to read
+ * at all.  Same rule as the query-compiled kernels (jit.cpp). */
 __device__ __forceinline__ double eval_agg(const sn_dev_plan *P,
                                            const sn_dev_agg &A,
                                            const double *sval, int r) {
-  return (A.a0 + A.m0 * sv_agg(P, sval, A.c0, r)) *
-         (A.a1 + A.m1 * sv_agg(P, sval, A.c1, r)) *
-         (A.a2 + A.m2 * sv_agg(P, sval, A.c2, r));
+  if (A.nf < 1) return 1.0;
+  double v = A.a0 + A.m0 * sv_agg(P, sval, A.c0, r);
+  if (A.nf >= 2) v *= A.a1 + A.m1 * sv_agg(P, sval, A.c1, r);
+  if (A.nf >= 3) v *= A.a2 + A.m2 * sv_agg(P, sval, A.c2, r);
+  return v;
 }
 
 /* order-preserving double<->u64 for MIN/MAX accumulators (device twin of

@@ -244,6 +244,52 @@ def test_carries_grouped(eng, carry_data):
         assert int(drows[(str(g),)][0]) != exp[0]
 
 
+def test_carries_over_compressed_batches(eng, carry_data):
+    """The same sums over batch_put blobs that arrive compressed: column 0
+    LZ4-wrapped (decoded on the device), column 1 Snappy-wrapped (decoded on
+    the host), key column plain.  The exact 192-bit sums make this a
+    byte-level check of the decoded INT64 bodies as the scan sees them,
+    the 16-byte body alignment pad included."""
+    from tests.test_compression import wrap_lz4, wrap_snappy
+    a, b, k = carry_data
+    t = eng.table_define("carry_z", [(abi.T_INT64, False), (abi.T_INT64, False),
+                                     (abi.T_INT32, False)])
+    s = 0
+    packed = plain = 0
+    for bi, n in enumerate(SIZES):
+        blobs = [po.encode(po.T_INT64, po.ENC_UNCOMPRESSED, a[s:s + n]),
+                 po.encode(po.T_INT64, po.ENC_UNCOMPRESSED, b[s:s + n]),
+                 po.encode(po.T_INT32, po.ENC_UNCOMPRESSED, k[s:s + n])]
+        wrapped = [wrap_lz4(blobs[0]), wrap_snappy(blobs[1]), blobs[2]]
+        assert wrapped[0][:4] == (-1).to_bytes(4, "little", signed=True)
+        assert wrapped[1][:4] == (-2).to_bytes(4, "little", signed=True)
+        plain += len(blobs[0]) + len(blobs[1])
+        packed += len(wrapped[0]) + len(wrapped[1])
+        # ColumnStatsSchema row, as a real put carries it: the grouped
+        # decimal scan needs the key column's bounds for its dense slots
+        part = [a[s:s + n], b[s:s + n], k[s:s + n]]
+        stats = po.encode_stats([po.T_INT64, po.T_INT64, po.T_INT32], n,
+                                [int(c.min()) for c in part],
+                                [int(c.max()) for c in part])
+        eng.batch_put(t, bi, bi, n, wrapped, stats=stats)
+        s += n
+    assert s == N and packed < plain               # the big batches do compress
+    eng.table_set_decimal(t, 0, 16, 3)
+    eng.table_set_decimal(t, 1, 16, 3)
+
+    plan, aggs = abi.make_dec_plan(table=t, aggs=CARRY_AGGS)
+    (keys, vals, scales), = eng.query_dec(plan, aggs).dec_rows()
+    assert vals == carry_ref(a, b)
+    assert scales == [6, 3, 3, 3, 0]
+
+    plan, aggs = abi.make_dec_plan(table=t, group_cols=[2], aggs=CARRY_AGGS)
+    rows = by_key(eng.query_dec(plan, aggs).dec_rows())
+    assert len(rows) == 8
+    for g in range(8):
+        m = k == g
+        assert rows[(str(g),)][0] == carry_ref(a[m], b[m]), g
+
+
 # -------------------------------------------------------------- 3. overflow
 
 

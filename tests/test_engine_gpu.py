@@ -938,3 +938,28 @@ def test_concurrent_submits_different_tables():
         assert not errs, errs
     finally:
         e.close()
+
+
+def test_count_star_unaffected_by_nonfinite_column_values(eng):
+    """COUNT(*) has no input factor, so an infinite value in a column the
+    plan merely filters on must not reach it: the interpreted kernels used
+    to evaluate the unused factors as (1 + 0*x), which is NaN for x = inf.
+    The nullable column keeps the plan on the interpreted kernels."""
+    n = 5000
+    rng = np.random.default_rng(61)
+    x = rng.random(n)
+    x[::7] = np.inf
+    x[3::11] = np.nan
+    y = rng.integers(0, 100, n).astype(np.int32)
+    valid = (rng.random(n) > 0.2).astype(np.uint8)
+    t = eng.table_define("tinf", [(abi.T_DOUBLE, False), (abi.T_INT32, True)])
+    assert eng.ingest_columns(t, [{"data": x}, {"data": y, "valid": valid}],
+                              n, batch_rows=2000) == n
+    rows = eng.query(abi.make_plan(
+        table=t, preds=[dict(col=0, is_double=True, lo=0.5), dict(col=1, hi=50)],
+        aggs=[("count", []), ("sum", [(1, 0.0, 1.0)])])).rows()
+    with np.errstate(invalid="ignore"):
+        m = (x >= 0.5) & (valid == 1) & (y <= 50)      # NaN and NULL fail
+    assert np.isinf(x[m]).any()
+    assert rows[0][1][0] == float(m.sum())
+    assert rows[0][1][1] == float(y[m].sum())
