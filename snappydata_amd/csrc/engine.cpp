@@ -205,9 +205,11 @@ struct Batch {
   std::vector<std::vector<uint8_t>> host_blobs;
 };
 
-/* cached device descriptor set for one plan shape (the reference caches
- * generated plans per query signature, SnappySession plan cache) */
-struct DescCache {
+/* what a launch needs to know about the batches it scans: the device
+ * descriptor set for one plan shape, built fresh or cached on the table by
+ * `sig` (the reference caches generated plans per query signature,
+ * SnappySession plan cache) */
+struct ScanSet {
   uint64_t sig = 0;
   size_t batch_count = 0;       /* invalidation: table grew */
   const void *db_dev = nullptr;
@@ -228,7 +230,7 @@ struct Table {
   std::string name;
   std::vector<sn_col_schema> schema;
   std::vector<Batch> batches;
-  std::vector<DescCache> desc_caches;
+  std::vector<ScanSet> desc_caches;
   /* global dictionary per column (string dict cols) */
   std::vector<std::vector<std::string>> gdict;
   std::vector<std::map<std::string, int32_t>> gdict_idx;
@@ -496,6 +498,105 @@ static inline uint64_t mix64h(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+/* device descriptor of column c of batch b: body/null pointers, encoding ->
+ * SN_K_* kind, RLE aux, dictionary map, patch pointers.  The one place a new
+ * encoding or kind is added — the query descriptor build and the join build
+ * both come through here.  A dictionary column's map carries its global ids
+ * times `mul` with nulls at `null_gid` (dict_premul; join builds pass 1, 0);
+ * premul_patches uploads string patch values times `mul` for this query
+ * instead of pointing at the stored global ids.  Clears *clean when the
+ * column carries nulls or patches. */
+static int fill_dev_col(sn_engine *e, const Table *t, Batch &b, int c, int mul,
+                        int null_gid, bool premul_patches, sn_dev_col *out,
+                        bool *clean) {
+  const ColMeta &m = b.cols[c];
+  sn_dev_col &dc = *out;
+  memset(&dc, 0, sizeof(dc));
+  sn_type_t dt = t->schema[c].dtype;
+  dc.body = (const uint8_t *)b.col_dev[c] + m.body_off;
+  dc.has_nulls = m.num_null_words > 0;
+  if (dc.has_nulls) {
+    dc.nullw = (const uint64_t *)((const uint8_t *)b.col_dev[c] + m.null_off);
+    dc.nullpfx = b.nullpfx_dev[c];
+    *clean = false;
+  }
+  switch (m.type_id) {
+    case SN_ENC_UNCOMPRESSED:
+      switch (dt) {
+        case SN_TYPE_DOUBLE: dc.kind = SN_K_F64; break;
+        case SN_TYPE_INT32: dc.kind = SN_K_I32; break;
+        case SN_TYPE_INT64: dc.kind = SN_K_I64; break;
+        case SN_TYPE_FLOAT: dc.kind = SN_K_F32; break;
+        case SN_TYPE_INT16: dc.kind = SN_K_I16; break;
+        case SN_TYPE_BOOL: dc.kind = SN_K_U8; break;
+        case SN_TYPE_INT8: dc.kind = SN_K_S8; break;
+        default:
+          return fail(SN_ERR_UNSUPPORTED, "uncompressed %d on GPU path", (int)dt);
+      }
+      break;
+    case SN_ENC_RUNLENGTH:
+      if (b.rle_n[c] <= 0 && b.num_rows > 0)
+        return fail(SN_ERR_UNSUPPORTED, "RLE col %d has no run aux", c);
+      /* INT64 runs carry raw bits in rle_vals (put-time extraction) —
+       * a distinct kind so read_general bitcasts instead of rounding */
+      dc.kind = dt == SN_TYPE_INT64 ? SN_K_RLE_I64 : SN_K_RLE;
+      dc.rle_ends = b.rle_ends_dev[c];
+      dc.rle_vals = b.rle_vals_dev[c];
+      dc.rle_n = b.rle_n[c];
+      break;
+    case SN_ENC_BOOLEAN_BITSET:
+      dc.kind = SN_K_BOOLBIT;
+      break;
+    case SN_ENC_DICTIONARY:
+    case SN_ENC_BIG_DICTIONARY: {
+      if (dt != SN_TYPE_STRING)
+        return fail(SN_ERR_UNSUPPORTED,
+                    "int dictionary col %d on GPU path not yet supported", c);
+      dc.kind = m.type_id == SN_ENC_DICTIONARY ? SN_K_DICT16 : SN_K_DICT32;
+      /* local->premultiplied-global map, cached per (mul, null_gid) —
+       * local2global is fixed per batch, so queries with the same
+       * group geometry reuse one device map */
+      dc.null_gid = null_gid;
+      auto &mcache = b.dictmap_cache[c];
+      auto mit = mcache.find({ mul, null_gid });
+      if (mit != mcache.end()) {
+        dc.dictmap = mit->second;
+      } else {
+        std::vector<int32_t> map(m.local2global.size() + 1);
+        for (size_t i = 0; i < m.local2global.size(); i++)
+          map[i] = m.local2global[i] * mul;
+        /* index == numElements denotes null (DictionaryEncoding.scala:90) */
+        map[m.local2global.size()] = null_gid;
+        dc.dictmap = (const int32_t *)up(e, map.data(), map.size() * 4);
+        if (!dc.dictmap) return fail(SN_ERR_NOMEM, "dictmap upload");
+        mcache.emplace(std::make_pair(mul, null_gid), dc.dictmap);
+      }
+      break;
+    }
+    default:
+      return fail(SN_ERR_UNSUPPORTED, "encoding %d on GPU path not yet supported",
+                  m.type_id);
+  }
+  if (b.patch_dev[c].n > 0) {
+    *clean = false;
+    const Batch::PatchDev &pd = b.patch_dev[c];
+    dc.patch_bm = pd.bm;
+    dc.patch_pos = pd.pos;
+    dc.patch_nullbm = pd.nullbm;
+    dc.patch_n = pd.n;
+    if (dt == SN_TYPE_STRING && premul_patches) {
+      /* premultiply global ids for this query */
+      std::vector<double> pv(b.patch_host[c].val.size());
+      for (size_t i = 0; i < pv.size(); i++)
+        pv[i] = b.patch_host[c].val[i] * mul;
+      dc.patch_val = (const double *)up(e, pv.data(), pv.size() * 8);
+    } else {
+      dc.patch_val = pd.val;   /* string patches carry global ids (mul 1) */
+    }
+  }
+  return SN_OK;
+}
+
 /* ---- partitioned-partitioned (colocated) join build: populate a Dim from
  * a resident column table, built ON DEVICE (k_join_build) — the
  * HashJoinExec per-task ObjectHashSet build + HashedObjectCache reuse
@@ -552,70 +653,11 @@ extern "C" int32_t sn_dim_from_table(sn_engine *e, int32_t dim, int32_t table,
     db.del_bm = b.del_bm_dev;
     bool clean = !b.has_deletes;
     for (int ui = 0; ui < dp.nused; ui++) {
-      int c = used[ui];
-      const ColMeta &m = b.cols[c];
-      sn_dev_col &dc = db.cols[ui];
-      memset(&dc, 0, sizeof(dc));
-      sn_type_t dt = t->schema[c].dtype;
-      dc.body = (const uint8_t *)b.col_dev[c] + m.body_off;
-      dc.has_nulls = m.num_null_words > 0;
-      if (dc.has_nulls) {
-        dc.nullw = (const uint64_t *)((const uint8_t *)b.col_dev[c] + m.null_off);
-        dc.nullpfx = b.nullpfx_dev[c];
-        clean = false;
-      }
-      switch (m.type_id) {
-        case SN_ENC_UNCOMPRESSED:
-          switch (dt) {
-            case SN_TYPE_INT32: dc.kind = SN_K_I32; break;
-            case SN_TYPE_INT64: dc.kind = SN_K_I64; break;
-            case SN_TYPE_INT16: dc.kind = SN_K_I16; break;
-            default:
-              return fail(SN_ERR_UNSUPPORTED, "build col %d dtype", c);
-          }
-          break;
-        case SN_ENC_RUNLENGTH:
-          if (b.rle_n[c] <= 0 && b.num_rows > 0)
-            return fail(SN_ERR_UNSUPPORTED, "RLE col %d without run aux", c);
-          dc.kind = dt == SN_TYPE_INT64 ? SN_K_RLE_I64 : SN_K_RLE;
-          dc.rle_ends = b.rle_ends_dev[c];
-          dc.rle_vals = b.rle_vals_dev[c];
-          dc.rle_n = b.rle_n[c];
-          break;
-        case SN_ENC_DICTIONARY:
-        case SN_ENC_BIG_DICTIONARY: {
-          if (dt != SN_TYPE_STRING)
-            return fail(SN_ERR_UNSUPPORTED, "unexpected dict col %d", c);
-          dc.kind = m.type_id == SN_ENC_DICTIONARY ? SN_K_DICT16 : SN_K_DICT32;
-          /* payload gid = table-global dictionary id (mul 1, null slot 0) */
-          auto &mcache = b.dictmap_cache[c];
-          auto mit = mcache.find({ 1, 0 });
-          if (mit != mcache.end()) {
-            dc.dictmap = mit->second;
-          } else {
-            std::vector<int32_t> map(m.local2global.size() + 1);
-            for (size_t i = 0; i < m.local2global.size(); i++)
-              map[i] = m.local2global[i];
-            map[m.local2global.size()] = 0;
-            dc.dictmap = (const int32_t *)up(e, map.data(), map.size() * 4);
-            if (!dc.dictmap) return fail(SN_ERR_NOMEM, "dictmap upload");
-            mcache.emplace(std::make_pair(1, 0), dc.dictmap);
-          }
-          dc.null_gid = 0;
-          break;
-        }
-        default:
-          return fail(SN_ERR_UNSUPPORTED, "encoding %d on build path", m.type_id);
-      }
-      if (b.patch_dev[c].n > 0) {
-        clean = false;
-        const Batch::PatchDev &pd = b.patch_dev[c];
-        dc.patch_bm = pd.bm;
-        dc.patch_pos = pd.pos;
-        dc.patch_nullbm = pd.nullbm;
-        dc.patch_n = pd.n;
-        dc.patch_val = pd.val;   /* string patches carry global ids (mul 1) */
-      }
+      /* payload gid = table-global dictionary id (mul 1, null slot 0); the
+       * dtype checks above leave only int16/int32/int64 keys and a string
+       * attribute to reach the fill */
+      int rc = fill_dev_col(e, t, b, used[ui], 1, 0, false, &db.cols[ui], &clean);
+      if (rc != SN_OK) return rc;
     }
     db.clean = clean ? 1 : 0;
     int32_t bi = (int32_t)hb.size();
@@ -1932,154 +1974,127 @@ static int ensure_sparse_ws(sn_engine *e, int cap_log2, int naggs1) {
   return SN_OK;
 }
 
-/* shared submit body.  dec == NULL is sn_query_submit; otherwise `plan`
- * carries a double-typed image of the decimal aggregates (so column
- * collection, slot derivation, descriptor build and stats skipping are the
- * double path's own code) and the launch section routes to the exact
- * decimal kernels. */
-static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
-                             const DecReq *dec) {
-  if (!e || !plan) { fail(SN_ERR_BADARG, "null engine/plan"); return nullptr; }
-  Table *t = get_table(e, plan->table);
-  if (!t) { fail(SN_ERR_BADARG, "unknown table %d", plan->table); return nullptr; }
-  if (!e->has_gpu) { fail(SN_ERR_NOGPU, "no HIP device — the engine never falls back to CPU"); return nullptr; }
-  /* one submit at a time per engine (shared stream/scratch/workspaces) */
-  std::lock_guard<std::mutex> qg(e->query_mu);
-  if (plan->npreds > SN_MAX_PREDS || plan->naggs > SN_MAX_AGGS ||
-      plan->ngroup > SN_MAX_GROUPS || plan->naggs <= 0) {
-    fail(SN_ERR_BADARG, "plan limits exceeded"); return nullptr;
+/* ---- submit phases ----
+ * submit_impl (below) calls these in order.  Each returns SN_OK or the code
+ * it has already passed to fail(). */
+
+static int use_col(sn_query *q, int c) {
+  if (c < 0 || c >= (int)q->t->schema.size()) return -1;
+  if (q->cslot_of_col[c] < 0) {
+    if ((int)q->used_cols.size() >= SN_DEV_MAX_COLS) return -1;
+    q->cslot_of_col[c] = (int)q->used_cols.size();
+    q->used_cols.push_back(c);
   }
+  return q->cslot_of_col[c];
+}
 
-  auto q = std::make_unique<sn_query>();
-  q->e = e; q->t = t; q->plan = *plan;
+/* collect referenced columns -> device col slots */
+static int32_t collect_plan_columns(sn_query *q) {
+  const Table *t = q->t;
+  const sn_plan *plan = &q->plan;
   for (int i = 0; i < 64; i++) q->cslot_of_col[i] = -1;
-
-  /* collect referenced columns -> device col slots */
-  auto use_col = [&](int c) -> int {
-    if (c < 0 || c >= (int)t->schema.size()) return -1;
-    if (q->cslot_of_col[c] < 0) {
-      if ((int)q->used_cols.size() >= SN_DEV_MAX_COLS) return -1;
-      q->cslot_of_col[c] = (int)q->used_cols.size();
-      q->used_cols.push_back(c);
-    }
-    return q->cslot_of_col[c];
-  };
   for (int i = 0; i < plan->npreds; i++) {
     const sn_pred &pr = plan->preds[i];
-    if (use_col(pr.col) < 0) { fail(SN_ERR_BADARG, "bad pred col"); return nullptr; }
+    if (use_col(q, pr.col) < 0) return fail(SN_ERR_BADARG, "bad pred col");
     if (t->schema[pr.col].dtype == SN_TYPE_STRING &&
-        (!pr.str_eq || pr.str_len <= 0) && pr.in_n <= 0) {
-      fail(SN_ERR_UNSUPPORTED,
-           "string predicate supports dictionary equality (str_eq) and "
-           "IN-lists (in_s) only");
-      return nullptr;
-    }
+        (!pr.str_eq || pr.str_len <= 0) && pr.in_n <= 0)
+      return fail(SN_ERR_UNSUPPORTED,
+                  "string predicate supports dictionary equality (str_eq) and "
+                  "IN-lists (in_s) only");
   }
   for (int i = 0; i < plan->ngroup; i++) {
     int c = plan->group_cols[i];
     sn_type_t gdt = t->schema[c].dtype;
     bool int_key = gdt == SN_TYPE_INT32 || gdt == SN_TYPE_INT16 ||
                    gdt == SN_TYPE_INT64;
-    if (gdt != SN_TYPE_STRING && !int_key) {
-      fail(SN_ERR_UNSUPPORTED,
-           "group-by supports dictionary string and int16/int32/int64 key columns");
-      return nullptr;
-    }
-    if (int_key && t->schema[c].nullable && plan->ngroup != 1) {
+    if (gdt != SN_TYPE_STRING && !int_key)
+      return fail(SN_ERR_UNSUPPORTED,
+                  "group-by supports dictionary string and int16/int32/int64 key columns");
+    if (int_key && t->schema[c].nullable && plan->ngroup != 1)
       /* a NULL in one key of a pair is a distinct composite group the
        * packed sparse key cannot represent */
-      fail(SN_ERR_UNSUPPORTED,
-           "nullable integer group keys supported for single-column "
-           "group-bys only");
-      return nullptr;
-    }
-    if (use_col(c) < 0) { fail(SN_ERR_BADARG, "bad group col"); return nullptr; }
+      return fail(SN_ERR_UNSUPPORTED,
+                  "nullable integer group keys supported for single-column "
+                  "group-bys only");
+    if (use_col(q, c) < 0) return fail(SN_ERR_BADARG, "bad group col");
   }
-  if (plan->ngroup == 2 && plan->group_cols[0] == plan->group_cols[1]) {
+  if (plan->ngroup == 2 && plan->group_cols[0] == plan->group_cols[1])
     /* both keys share one device column slot, which cannot carry two
      * different premultiplied dictionary images — found by the parity
      * fuzzer producing off-diagonal keys.  GROUP BY a, a is degenerate;
      * reject loudly so the planner dedups upstream. */
-    fail(SN_ERR_UNSUPPORTED, "duplicate group column (dedup upstream)");
-    return nullptr;
-  }
+    return fail(SN_ERR_UNSUPPORTED, "duplicate group column (dedup upstream)");
   for (int a = 0; a < plan->naggs; a++)
     for (int f = 0; f < plan->aggs[a].nfactors; f++) {
       int c = plan->aggs[a].factors[f].col;
       sn_type_t dt = t->schema[c].dtype;
-      if (dt == SN_TYPE_STRING) { fail(SN_ERR_UNSUPPORTED, "string agg input"); return nullptr; }
-      if (use_col(c) < 0) { fail(SN_ERR_BADARG, "too many plan columns"); return nullptr; }
+      if (dt == SN_TYPE_STRING) return fail(SN_ERR_UNSUPPORTED, "string agg input");
+      if (use_col(q, c) < 0) return fail(SN_ERR_BADARG, "too many plan columns");
     }
+  return SN_OK;
+}
 
-  /* broadcast-dimension join */
-  Dim *jd = nullptr;
-  if (plan->join_dim != SN_JOIN_NONE) {
-    if (plan->join_dim < 0 || plan->join_dim >= (int32_t)e->dims.size()) {
-      fail(SN_ERR_BADARG, "unknown dimension %d", plan->join_dim); return nullptr;
+/* broadcast-dimension join: q->join_dim stays null without one */
+static int32_t resolve_join(sn_query *q) {
+  sn_engine *e = q->e;
+  const Table *t = q->t;
+  const sn_plan *plan = &q->plan;
+  if (plan->join_dim == SN_JOIN_NONE) return SN_OK;
+  if (plan->join_dim < 0 || plan->join_dim >= (int32_t)e->dims.size())
+    return fail(SN_ERR_BADARG, "unknown dimension %d", plan->join_dim);
+  Dim *jd = e->dims[plan->join_dim].get();
+  if (jd->keys.empty() && !jd->dev_keys)
+    return fail(SN_ERR_BADARG, "empty dimension");
+  sn_type_t kt = t->schema[plan->join_fact_col].dtype;
+  if (kt != SN_TYPE_INT32 && kt != SN_TYPE_INT64)
+    return fail(SN_ERR_UNSUPPORTED, "join key must be int32/int64");
+  if (plan->join_mode == SN_JOIN_GROUP && plan->ngroup > 1)
+    return fail(SN_ERR_UNSUPPORTED,
+                "dim-attr grouping supports at most ONE fact group column "
+                "(attr + fact key fill the 2-key result row)");
+  if (use_col(q, plan->join_fact_col) < 0)
+    return fail(SN_ERR_BADARG, "too many plan columns");
+  if (plan->join_mode == SN_JOIN_GROUP && jd->attr_maxlen > SN_KEY_MAX - 1)
+    return fail(SN_ERR_UNSUPPORTED,
+                "dimension attribute exceeds the %d-byte group-key limit",
+                SN_KEY_MAX - 1);
+  int rc = dim_device_table(e, jd);
+  if (rc != SN_OK) return rc;
+  q->join_dim = jd;
+  q->join_group = plan->join_mode == SN_JOIN_GROUP;
+  return SN_OK;
+}
+
+/* integer group keys: the slot space is the stats-derived value range
+ * (the DictionaryOptimizedMapAccessor direct-slot idea applied to ints).
+ * Requires every batch to carry valid bounds for the key column and no
+ * update patches on it (patches may move values outside the bounds).
+ * Returns the dense-slot span of an integer key column, or -1 when the dense
+ * path is unavailable (missing stats bounds, update patches, overflowing
+ * span) — the caller then falls back to the open-address hash aggregate */
+static int64_t int_key_span(const Table *t, int c, int64_t *mn_out) {
+  int64_t mn = 0, mx = -1;
+  bool first = true;
+  for (auto &b : t->batches) {
+    if (!b.stats_valid || b.bounds_null[c]) return -1;
+    if (b.had_patches.size() > (size_t)c && b.had_patches[c]) return -1;
+    if (first) { mn = b.lo_i[c]; mx = b.hi_i[c]; first = false; }
+    else {
+      mn = b.lo_i[c] < mn ? b.lo_i[c] : mn;
+      mx = b.hi_i[c] > mx ? b.hi_i[c] : mx;
     }
-    jd = e->dims[plan->join_dim].get();
-    if (jd->keys.empty() && !jd->dev_keys) {
-      fail(SN_ERR_BADARG, "empty dimension"); return nullptr;
-    }
-    sn_type_t kt = t->schema[plan->join_fact_col].dtype;
-    if (kt != SN_TYPE_INT32 && kt != SN_TYPE_INT64) {
-      fail(SN_ERR_UNSUPPORTED, "join key must be int32/int64"); return nullptr;
-    }
-    if (plan->join_mode == SN_JOIN_GROUP && plan->ngroup > 1) {
-      fail(SN_ERR_UNSUPPORTED,
-           "dim-attr grouping supports at most ONE fact group column "
-           "(attr + fact key fill the 2-key result row)");
-      return nullptr;
-    }
-    if (use_col(plan->join_fact_col) < 0) {
-      fail(SN_ERR_BADARG, "too many plan columns"); return nullptr;
-    }
-    if (plan->join_mode == SN_JOIN_GROUP && jd->attr_maxlen > SN_KEY_MAX - 1) {
-      fail(SN_ERR_UNSUPPORTED,
-           "dimension attribute exceeds the %d-byte group-key limit",
-           SN_KEY_MAX - 1);
-      return nullptr;
-    }
-    if (dim_device_table(e, jd) != SN_OK) return nullptr;
-    q->join_dim = jd;
-    q->join_group = plan->join_mode == SN_JOIN_GROUP;
   }
+  if (first) { *mn_out = 0; return 1; }   /* empty table */
+  *mn_out = mn;
+  return mx - mn + 1;
+}
 
-  /* ONE t->mu critical section from group-slot derivation through the
-   * descriptor build below: a concurrent sn_batch_put (config-5
-   * ingest+scan) may grow the global dictionary and append batches; slot
-   * capacities, premultiplied dictmaps and the descriptor set must all see
-   * the same consistent table state or grouped kernels write accumulator
-   * rows out of bounds. */
-  std::lock_guard<std::mutex> g(t->mu);
-  sync_pending_stats(e, t);   /* raw-ingested batches: resolve device bounds */
-
-  /* group slot space: global dict sizes, plus a null slot only when the
-   * schema allows null keys (non-nullable key columns waste no slots —
-   * keeps Q1's 3x2 keys in the register-friendly 8x8 kernel) */
-  /* integer group keys: the slot space is the stats-derived value range
-     (the DictionaryOptimizedMapAccessor direct-slot idea applied to ints).
-     Requires every batch to carry valid bounds for the key column and no
-     update patches on it (patches may move values outside the bounds). */
-  /* dense-slot span of an integer key column, or -1 when the dense path is
-   * unavailable (missing stats bounds, update patches, overflowing span) —
-   * the caller then falls back to the open-address hash aggregate */
-  auto int_key_span = [&](int c, int64_t *mn_out) -> int64_t {
-    int64_t mn = 0, mx = -1;
-    bool first = true;
-    for (auto &b : t->batches) {
-      if (!b.stats_valid || b.bounds_null[c]) return -1;
-      if (b.had_patches.size() > (size_t)c && b.had_patches[c]) return -1;
-      if (first) { mn = b.lo_i[c]; mx = b.hi_i[c]; first = false; }
-      else {
-        mn = b.lo_i[c] < mn ? b.lo_i[c] : mn;
-        mx = b.hi_i[c] > mx ? b.hi_i[c] : mx;
-      }
-    }
-    if (first) { *mn_out = 0; return 1; }   /* empty table */
-    *mn_out = mn;
-    return mx - mn + 1;
-  };
+/* group slot space: global dict sizes, plus a null slot only when the
+ * schema allows null keys (non-nullable key columns waste no slots —
+ * keeps Q1's 3x2 keys in the register-friendly 8x8 kernel) */
+static int32_t derive_group_slots(sn_query *q, bool dec) {
+  const Table *t = q->t;
+  const sn_plan *plan = &q->plan;
   if (plan->ngroup >= 1) {
     /* group keys travel as fixed SN_KEY_MAX-byte strings in results and
      * partial blocks; distinct keys sharing a 47-byte prefix would silently
@@ -2088,12 +2103,10 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
     for (int i = 0; i < plan->ngroup; i++) {
       int gc = plan->group_cols[i];
       if (t->schema[gc].dtype == SN_TYPE_STRING &&
-          t->gdict_maxlen[gc] > SN_KEY_MAX - 1) {
-        fail(SN_ERR_UNSUPPORTED,
-             "group key col %d has a %d-byte dictionary entry > %d-byte key limit",
-             gc, t->gdict_maxlen[gc], SN_KEY_MAX - 1);
-        return nullptr;
-      }
+          t->gdict_maxlen[gc] > SN_KEY_MAX - 1)
+        return fail(SN_ERR_UNSUPPORTED,
+                    "group key col %d has a %d-byte dictionary entry > %d-byte key limit",
+                    gc, t->gdict_maxlen[gc], SN_KEY_MAX - 1);
     }
     /* try the dense direct-slot space (dictionary ids / stats-ranged
      * integers); integer keys whose span is unbounded, statless, patched or
@@ -2111,7 +2124,7 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
         continue;
       }
       int64_t span = (gdt == SN_TYPE_INT64 || t->schema[c].nullable)
-                         ? -1 : int_key_span(c, &q->gmin[i]);
+                         ? -1 : int_key_span(t, c, &q->gmin[i]);
       if (span < 0 || span > SN_BIG_GROUP_CAP) { col_sparse[i] = true; continue; }
       q->gint[i] = true;
       caps[i] = (int)span;
@@ -2120,31 +2133,23 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
                           (int64_t)std::max(caps[1], 1);
     q->sparse = col_sparse[0] || col_sparse[1] ||
                 (!any_string && dense_slots > SN_BIG_GROUP_CAP);
-    if (q->sparse && dec) {
-      fail(SN_ERR_UNSUPPORTED,
-           "decimal aggregation needs dense group slots (dictionary strings "
-           "or stats-dense int16/int32 keys); sparse-hash group keys are "
-           "not supported");
-      return nullptr;
-    }
+    if (q->sparse && dec)
+      return fail(SN_ERR_UNSUPPORTED,
+                  "decimal aggregation needs dense group slots (dictionary strings "
+                  "or stats-dense int16/int32 keys); sparse-hash group keys are "
+                  "not supported");
     if (q->sparse) {
-      if (any_string) {
-        fail(SN_ERR_UNSUPPORTED,
-             "mixed string + sparse integer group keys not supported");
-        return nullptr;
-      }
+      if (any_string)
+        return fail(SN_ERR_UNSUPPORTED,
+                    "mixed string + sparse integer group keys not supported");
       if (plan->ngroup == 2 &&
           (t->schema[plan->group_cols[0]].dtype == SN_TYPE_INT64 ||
-           t->schema[plan->group_cols[1]].dtype == SN_TYPE_INT64)) {
-        fail(SN_ERR_UNSUPPORTED,
-             "two-column group keys with an int64 column not supported "
-             "(keys pack into one 64-bit word)");
-        return nullptr;
-      }
-      if (jd) {
-        fail(SN_ERR_UNSUPPORTED, "join combined with sparse group keys");
-        return nullptr;
-      }
+           t->schema[plan->group_cols[1]].dtype == SN_TYPE_INT64))
+        return fail(SN_ERR_UNSUPPORTED,
+                    "two-column group keys with an int64 column not supported "
+                    "(keys pack into one 64-bit word)");
+      if (q->join_dim)
+        return fail(SN_ERR_UNSUPPORTED, "join combined with sparse group keys");
       q->gint[0] = q->gint[1] = false;
       q->nslots = 0;
       q->g1cap = q->g2cap = 1;
@@ -2159,19 +2164,15 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
       if (q->g1cap == 0) q->g1cap = 1;
       if (q->g2cap == 0) q->g2cap = 1;
       q->nslots = q->g1cap * q->g2cap;
-      if (q->nslots > SN_BIG_GROUP_CAP) {
-        fail(SN_ERR_UNSUPPORTED, "group cardinality %d > %d",
-             q->nslots, SN_BIG_GROUP_CAP);
-        return nullptr;
-      }
+      if (q->nslots > SN_BIG_GROUP_CAP)
+        return fail(SN_ERR_UNSUPPORTED, "group cardinality %d > %d",
+                    q->nslots, SN_BIG_GROUP_CAP);
     }
   } else if (q->join_group) {
     q->nslots = (int)q->join_dim->attr_dict.size();
-    if (q->nslots > SN_MAX_GROUP_SLOTS) {
-      fail(SN_ERR_UNSUPPORTED, "dim attr cardinality %d > %d",
-           q->nslots, SN_MAX_GROUP_SLOTS);
-      return nullptr;
-    }
+    if (q->nslots > SN_MAX_GROUP_SLOTS)
+      return fail(SN_ERR_UNSUPPORTED, "dim attr cardinality %d > %d",
+                  q->nslots, SN_MAX_GROUP_SLOTS);
   } else {
     q->nslots = 1;
   }
@@ -2179,53 +2180,52 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
     /* composite GROUP BY dim_attr, fact_col: attr-major slots over the
      * dense fact slot space (sparse fact keys were rejected above) */
     const int attr_cap = (int)q->join_dim->attr_dict.size();
-    if (attr_cap > SN_MAX_GROUP_SLOTS) {
-      fail(SN_ERR_UNSUPPORTED, "dim attr cardinality %d > %d",
-           attr_cap, SN_MAX_GROUP_SLOTS);
-      return nullptr;
-    }
+    if (attr_cap > SN_MAX_GROUP_SLOTS)
+      return fail(SN_ERR_UNSUPPORTED, "dim attr cardinality %d > %d",
+                  attr_cap, SN_MAX_GROUP_SLOTS);
     q->fact_slots = q->nslots;
     const int64_t total = (int64_t)attr_cap * q->fact_slots;
-    if (total > SN_BIG_GROUP_CAP) {
-      fail(SN_ERR_UNSUPPORTED, "attr x fact group cardinality %lld > %d",
-           (long long)total, SN_BIG_GROUP_CAP);
-      return nullptr;
-    }
+    if (total > SN_BIG_GROUP_CAP)
+      return fail(SN_ERR_UNSUPPORTED, "attr x fact group cardinality %lld > %d",
+                  (long long)total, SN_BIG_GROUP_CAP);
     q->nslots = (int)total;
   }
-  /* (na_t set after device-aggregate dedup below) */
+  return SN_OK;
+}
 
-  /* build device plan — canonical branchless forms:
-   * predicates as closed intervals (strictness folded via nextafter / +-1,
-   * missing bounds as +-inf), aggregates as three neutral-padded factors */
-  sn_dev_plan dp;
-  memset(&dp, 0, sizeof(dp));
-  dp.naggs = plan->naggs;
-  dp.ngroup = plan->ngroup; dp.nslots = q->nslots;
-  dp.nused = (int32_t)q->used_cols.size();
-  dp.i64_mask = 0;
-  for (size_t ui = 0; ui < q->used_cols.size(); ui++)
-    if (t->schema[q->used_cols[ui]].dtype == SN_TYPE_INT64)
-      dp.i64_mask |= 1u << ui;
-  for (int i = 0; i < plan->ngroup; i++) dp.gcol[i] = q->cslot_of_col[plan->group_cols[i]];
-  dp.gmul0 = 1;
-  if (plan->ngroup >= 1 && q->gint[0]) {
-    dp.gbase[0] = q->gmin[0];
-    dp.gmul0 = q->g2cap;       /* dict col0 premultiplies via its dictmap */
-  }
-  if (plan->ngroup == 2 && q->gint[1]) dp.gbase[1] = q->gmin[1];
-  if (jd) {
-    dp.jkeys = jd->dev_keys;
-    dp.jpayload = jd->dev_payload;
-    dp.jcap_log2 = jd->cap_log2;
-    dp.jcslot = q->cslot_of_col[plan->join_fact_col];
-    dp.jmode = plan->join_mode == SN_JOIN_GROUP ? 1 : 0;
-    if (q->join_group && plan->ngroup >= 1)
-      dp.jslot_mul = q->fact_slots;   /* composite dim_attr x fact_col */
-    dp.jlut = jd->dev_lut;
-    dp.jlut_min = jd->lut_min;
-    dp.jlut_max = jd->lut_max;
-  }
+/* a dictionary column's global ids reach the kernels premultiplied by g2cap
+ * (so slot = id0 * g2cap + id1 needs no multiply per row) unless it is the
+ * second group column; its nulls map to the column's null slot likewise.
+ * Predicate literals, IN-lists, dictmaps and string patch values must all
+ * agree on this, so all of them ask here. */
+struct DictPremul { int mul, null_gid; };
+static DictPremul dict_premul(const sn_query *q, const sn_plan *plan, int col) {
+  const bool is_g2 = plan->ngroup == 2 && plan->group_cols[1] == col;
+  const int gn = is_g2 ? q->gnull2 : q->gnull1;
+  return { is_g2 ? 1 : (q->g2cap > 0 ? q->g2cap : 1),
+           gn >= 0 ? (is_g2 ? gn : gn * q->g2cap) : 0 };
+}
+
+/* global dict id of a string literal, -1 when no batch interned it */
+static int64_t dict_lookup(const Table *t, int col, const char *s, size_t len) {
+  auto it = t->gdict_idx[col].find(std::string(s, len));
+  return it != t->gdict_idx[col].end() ? it->second : -1;
+}
+
+/* upload a query-owned block (recycled at sn_query_destroy) */
+static const void *up_owned(sn_query *q, const void *host, size_t n) {
+  void *d = q->e->arena.alloc(n);
+  if (!d || hipMemcpy(d, host, n, hipMemcpyHostToDevice) != hipSuccess)
+    return nullptr;
+  q->owned.push_back({ d, n });
+  return d;
+}
+
+/* predicates as closed intervals (strictness folded via nextafter / +-1,
+ * missing bounds as +-inf) */
+static int32_t build_preds(sn_query *q, sn_dev_plan &dp) {
+  const Table *t = q->t;
+  const sn_plan *plan = &q->plan;
   for (int i = 0; i < plan->npreds; i++) {
     const sn_pred &s = plan->preds[i];
     sn_type_t dt = t->schema[s.col].dtype;
@@ -2235,24 +2235,19 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
        * dictionary strings resolved to premultiplied global ids (absent
        * literals drop out).  Dense value spans build a bitmap LUT; wide
        * spans keep a sorted list (binary-searched; interpreted kernels). */
-      if (dp.npreds_in >= 2) { fail(SN_ERR_BADARG, "too many IN predicates"); return nullptr; }
-      if (s.has_lo || s.has_hi) {
-        fail(SN_ERR_BADARG, "an IN predicate may not also carry range bounds");
-        return nullptr;
-      }
+      if (dp.npreds_in >= 2) return fail(SN_ERR_BADARG, "too many IN predicates");
+      if (s.has_lo || s.has_hi)
+        return fail(SN_ERR_BADARG, "an IN predicate may not also carry range bounds");
       std::vector<int64_t> vals;
       if (dt == SN_TYPE_STRING) {
-        if (!s.in_s || !s.in_s_len) { fail(SN_ERR_BADARG, "IN needs in_s"); return nullptr; }
-        bool is_g2 = plan->ngroup == 2 && plan->group_cols[1] == s.col;
-        int64_t mul = is_g2 ? 1 : (q->g2cap > 0 ? q->g2cap : 1);
+        if (!s.in_s || !s.in_s_len) return fail(SN_ERR_BADARG, "IN needs in_s");
+        const int64_t mul = dict_premul(q, plan, s.col).mul;
         for (int32_t vi = 0; vi < s.in_n; vi++) {
-          auto it = t->gdict_idx[s.col].find(
-              std::string(s.in_s[vi], (size_t)s.in_s_len[vi]));
-          if (it != t->gdict_idx[s.col].end())
-            vals.push_back((int64_t)it->second * mul);
+          int64_t gid = dict_lookup(t, s.col, s.in_s[vi], (size_t)s.in_s_len[vi]);
+          if (gid >= 0) vals.push_back(gid * mul);
         }
       } else {
-        if (!s.in_i) { fail(SN_ERR_BADARG, "IN needs in_i"); return nullptr; }
+        if (!s.in_i) return fail(SN_ERR_BADARG, "IN needs in_i");
         vals.assign(s.in_i, s.in_i + s.in_n);
       }
       std::sort(vals.begin(), vals.end());
@@ -2271,23 +2266,13 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
         const int64_t nwords = ((mx - mn) >> 6) + 1;
         std::vector<uint64_t> bm((size_t)nwords, 0);
         for (int64_t v : vals) bm[(v - mn) >> 6] |= 1ull << ((v - mn) & 63);
-        void *bmd = e->arena.alloc(bm.size() * 8);
-        if (!bmd || hipMemcpy(bmd, bm.data(), bm.size() * 8,
-                              hipMemcpyHostToDevice) != hipSuccess) {
-          fail(SN_ERR_NOMEM, "IN bitmap upload"); return nullptr;
-        }
-        q->owned.push_back({ bmd, bm.size() * 8 });
-        ip.bm = (const uint64_t *)bmd;
+        ip.bm = (const uint64_t *)up_owned(q, bm.data(), bm.size() * 8);
+        if (!ip.bm) return fail(SN_ERR_NOMEM, "IN bitmap upload");
         ip.base = mn;
         ip.nwords = (int32_t)nwords;
       } else {
-        void *ld = e->arena.alloc(vals.size() * 8);
-        if (!ld || hipMemcpy(ld, vals.data(), vals.size() * 8,
-                             hipMemcpyHostToDevice) != hipSuccess) {
-          fail(SN_ERR_NOMEM, "IN list upload"); return nullptr;
-        }
-        q->owned.push_back({ ld, vals.size() * 8 });
-        ip.list = (const int64_t *)ld;
+        ip.list = (const int64_t *)up_owned(q, vals.data(), vals.size() * 8);
+        if (!ip.list) return fail(SN_ERR_NOMEM, "IN list upload");
         ip.n = (int32_t)vals.size();
       }
       continue;
@@ -2295,14 +2280,8 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
     if (dt == SN_TYPE_STRING) {
       /* dictionary pushdown: literal -> global dict id, compared against
        * the (possibly premultiplied) id the conversion pass writes */
-      bool is_g2 = plan->ngroup == 2 && plan->group_cols[1] == s.col;
-      int64_t mul = is_g2 ? 1 : (q->g2cap > 0 ? q->g2cap : 1);
-      int64_t gid = -1;
-      {
-        auto it = t->gdict_idx[s.col].find(
-            std::string(s.str_eq, (size_t)s.str_len));
-        if (it != t->gdict_idx[s.col].end()) gid = it->second;
-      }
+      const int64_t mul = dict_premul(q, plan, s.col).mul;
+      const int64_t gid = dict_lookup(t, s.col, s.str_eq, (size_t)s.str_len);
       sn_dev_pred_d &d = dp.preds_d[dp.npreds_d++];
       d.cslot = cslot;
       if (gid < 0) { d.lo = 1.0; d.hi = 0.0; }   /* literal absent: no rows */
@@ -2310,7 +2289,7 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
       continue;
     }
     if (dt == SN_TYPE_INT64) {
-      if (dp.npreds_i >= 4) return (fail(SN_ERR_BADARG, "too many int64 preds"), nullptr);
+      if (dp.npreds_i >= 4) return fail(SN_ERR_BADARG, "too many int64 preds");
       sn_dev_pred_i &d = dp.preds_i[dp.npreds_i++];
       d.cslot = cslot;
       d.lo = s.has_lo ? (s.lo_strict && s.lo_i < INT64_MAX ? s.lo_i + 1 : s.lo_i)
@@ -2328,99 +2307,144 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
       d.lo = lo; d.hi = hi;
     }
   }
-  {
-    /* canonicalize each aggregate; in grouped mode dedupe identical
-     * expressions and fold COUNT(*) into the per-slot rowcount, so e.g.
-     * Q1's 8 logical aggregates run 5 device sweeps (sum/avg pairs share) */
-    const bool grouped = plan->ngroup > 0 || q->join_group;
-    int ndev = 0;
-    for (int a = 0; a < plan->naggs; a++) {
-      sn_dev_agg da;
-      da.a0 = da.a1 = da.a2 = 1.0;
-      da.m0 = da.m1 = da.m2 = 0.0;
-      da.c0 = da.c1 = da.c2 = 0;
-      da.nf = 0;
-      da._p2 = 0;
-      const sn_agg &sa = plan->aggs[a];
-      da.op = sa.kind == SN_AGG_MIN ? 1 : sa.kind == SN_AGG_MAX ? 2 : 0;
-      if (da.op != 0 && sa.nfactors < 1) {
-        fail(SN_ERR_BADARG, "MIN/MAX needs at least one factor");
-        return nullptr;
-      }
-      if (sa.kind != SN_AGG_COUNT_STAR) {
-        /* neutral factors get c = c0 below so their LDS reads CSE away */
-        da.nf = sa.nfactors;
-        if (sa.nfactors >= 1) {
-          da.c0 = q->cslot_of_col[sa.factors[0].col];
-          da.a0 = sa.factors[0].add; da.m0 = sa.factors[0].mul;
-          /* INT64 factors: kernels convert the raw-bit i64 LDS image to
-           * double per i64_mask.  A pure SUM(bigint_col) must stay
-           * BIT-EXACT (north star): f64 accumulation of integers is exact
-           * while every partial sum < 2^53, which the stats bounds prove;
-           * when they cannot, fail loudly rather than round silently.
-           * (Affine/multi-factor expressions are double-typed in SQL —
-           * the 1e-6 double budget applies, no gate.) */
-          if (!dec && (dp.i64_mask & (1u << da.c0)) && sa.kind == SN_AGG_SUM &&
-              sa.nfactors == 1 && sa.factors[0].add == 0.0 &&
-              sa.factors[0].mul == 1.0) {
-            int gc = sa.factors[0].col;
-            double bound = 0.0;
-            bool provable = true;
-            for (auto &bb : t->batches) {
-              if (!bb.stats_valid || bb.bounds_null[gc] ||
-                  (bb.had_patches.size() > (size_t)gc && bb.had_patches[gc])) {
-                provable = false;
-                break;
-              }
-              double mx = std::max(std::fabs((double)bb.lo_i[gc]),
-                                   std::fabs((double)bb.hi_i[gc]));
-              bound += (double)bb.num_rows * mx;
-            }
-            if (!provable || bound >= 9007199254740992.0 /* 2^53 */) {
-              fail(SN_ERR_UNSUPPORTED,
-                   "SUM over int64 col %d cannot be proven f64-exact "
-                   "(needs stats bounds with rows*max|v| < 2^53)", gc);
-              return nullptr;
-            }
-          }
-        }
-        if (sa.nfactors >= 2) {
-          da.c1 = q->cslot_of_col[sa.factors[1].col];
-          da.a1 = sa.factors[1].add; da.m1 = sa.factors[1].mul;
-        }
-        if (sa.nfactors >= 3) {
-          da.c2 = q->cslot_of_col[sa.factors[2].col];
-          da.a2 = sa.factors[2].add; da.m2 = sa.factors[2].mul;
-        }
-        if (sa.nfactors < 2) da.c1 = da.c0;
-        if (sa.nfactors < 3) da.c2 = sa.nfactors >= 2 ? da.c1 : da.c0;
-      }
-      if (grouped && sa.kind == SN_AGG_COUNT_STAR) {
-        q->agg_map[a] = -1;
-        continue;
-      }
-      int idx = -1;
-      if (grouped) {
-        for (int j = 0; j < ndev; j++)
-          if (memcmp(&dp.aggs[j], &da, sizeof(da)) == 0) { idx = j; break; }
-      }
-      if (idx < 0) { idx = ndev; dp.aggs[ndev++] = da; }
-      q->agg_map[a] = idx;
+  return SN_OK;
+}
+
+/* INT64 factors: kernels convert the raw-bit i64 LDS image to double per
+ * i64_mask.  A pure SUM(bigint_col) must stay BIT-EXACT (north star): f64
+ * accumulation of integers is exact while every partial sum < 2^53, which
+ * the stats bounds prove; when they cannot, fail loudly rather than round
+ * silently.  (Affine/multi-factor expressions are double-typed in SQL — the
+ * 1e-6 double budget applies, no gate.) */
+static int32_t prove_i64_sum_exact(const Table *t, int gc) {
+  double bound = 0.0;
+  bool provable = true;
+  for (auto &bb : t->batches) {
+    if (!bb.stats_valid || bb.bounds_null[gc] ||
+        (bb.had_patches.size() > (size_t)gc && bb.had_patches[gc])) {
+      provable = false;
+      break;
     }
-    q->dev_naggs = grouped ? ndev : plan->naggs;
-    dp.naggs = q->dev_naggs;
+    double mx = std::max(std::fabs((double)bb.lo_i[gc]),
+                         std::fabs((double)bb.hi_i[gc]));
+    bound += (double)bb.num_rows * mx;
   }
+  if (!provable || bound >= 9007199254740992.0 /* 2^53 */)
+    return fail(SN_ERR_UNSUPPORTED,
+                "SUM over int64 col %d cannot be proven f64-exact "
+                "(needs stats bounds with rows*max|v| < 2^53)", gc);
+  return SN_OK;
+}
+
+/* aggregates as three neutral-padded factors: canonicalize each; in grouped
+ * mode dedupe identical expressions and fold COUNT(*) into the per-slot
+ * rowcount, so e.g. Q1's 8 logical aggregates run 5 device sweeps (sum/avg
+ * pairs share) */
+static int32_t build_aggs(sn_query *q, sn_dev_plan &dp, bool dec) {
+  const sn_plan *plan = &q->plan;
+  const bool grouped = plan->ngroup > 0 || q->join_group;
+  int ndev = 0;
+  for (int a = 0; a < plan->naggs; a++) {
+    sn_dev_agg da;
+    da.a0 = da.a1 = da.a2 = 1.0;
+    da.m0 = da.m1 = da.m2 = 0.0;
+    da.c0 = da.c1 = da.c2 = 0;
+    da.nf = 0;
+    da._p2 = 0;
+    const sn_agg &sa = plan->aggs[a];
+    da.op = sa.kind == SN_AGG_MIN ? 1 : sa.kind == SN_AGG_MAX ? 2 : 0;
+    if (da.op != 0 && sa.nfactors < 1)
+      return fail(SN_ERR_BADARG, "MIN/MAX needs at least one factor");
+    if (sa.kind != SN_AGG_COUNT_STAR) {
+      /* neutral factors get c = c0 below so their LDS reads CSE away */
+      da.nf = sa.nfactors;
+      if (sa.nfactors >= 1) {
+        da.c0 = q->cslot_of_col[sa.factors[0].col];
+        da.a0 = sa.factors[0].add; da.m0 = sa.factors[0].mul;
+        if (!dec && (dp.i64_mask & (1u << da.c0)) && sa.kind == SN_AGG_SUM &&
+            sa.nfactors == 1 && sa.factors[0].add == 0.0 &&
+            sa.factors[0].mul == 1.0) {
+          int rc = prove_i64_sum_exact(q->t, sa.factors[0].col);
+          if (rc != SN_OK) return rc;
+        }
+      }
+      if (sa.nfactors >= 2) {
+        da.c1 = q->cslot_of_col[sa.factors[1].col];
+        da.a1 = sa.factors[1].add; da.m1 = sa.factors[1].mul;
+      }
+      if (sa.nfactors >= 3) {
+        da.c2 = q->cslot_of_col[sa.factors[2].col];
+        da.a2 = sa.factors[2].add; da.m2 = sa.factors[2].mul;
+      }
+      if (sa.nfactors < 2) da.c1 = da.c0;
+      if (sa.nfactors < 3) da.c2 = sa.nfactors >= 2 ? da.c1 : da.c0;
+    }
+    if (grouped && sa.kind == SN_AGG_COUNT_STAR) {
+      q->agg_map[a] = -1;
+      continue;
+    }
+    int idx = -1;
+    if (grouped) {
+      for (int j = 0; j < ndev; j++)
+        if (memcmp(&dp.aggs[j], &da, sizeof(da)) == 0) { idx = j; break; }
+    }
+    if (idx < 0) { idx = ndev; dp.aggs[ndev++] = da; }
+    q->agg_map[a] = idx;
+  }
+  q->dev_naggs = grouped ? ndev : plan->naggs;
+  dp.naggs = q->dev_naggs;
   for (int a = 0; a < q->dev_naggs; a++)
     if (dp.aggs[a].op != 0) q->mm = true;
-
   q->na_t = template_naggs(q->dev_naggs > 0 ? q->dev_naggs : 1);
   q->out_stride = 2 * (size_t)q->na_t + 1;
+  return SN_OK;
+}
 
-  /* batch descriptors + tile map.  Expensive at many batches (dict-map
-   * premultiply + uploads), so cache per plan signature; a cached set is
-   * only reusable when stats-skip removes nothing for THIS plan (skipping
-   * is an optimization — correctness is unaffected either way).
-   * (t->mu is still held — same critical section as the slot derivation.) */
+/* build device plan — canonical branchless forms (build_preds, build_aggs) */
+static int32_t build_dev_plan(sn_query *q, bool dec, sn_dev_plan &dp) {
+  const Table *t = q->t;
+  const sn_plan *plan = &q->plan;
+  memset(&dp, 0, sizeof(dp));
+  dp.naggs = plan->naggs;
+  dp.ngroup = plan->ngroup; dp.nslots = q->nslots;
+  dp.nused = (int32_t)q->used_cols.size();
+  dp.i64_mask = 0;
+  for (size_t ui = 0; ui < q->used_cols.size(); ui++)
+    if (t->schema[q->used_cols[ui]].dtype == SN_TYPE_INT64)
+      dp.i64_mask |= 1u << ui;
+  for (int i = 0; i < plan->ngroup; i++) dp.gcol[i] = q->cslot_of_col[plan->group_cols[i]];
+  dp.gmul0 = 1;
+  if (plan->ngroup >= 1 && q->gint[0]) {
+    dp.gbase[0] = q->gmin[0];
+    dp.gmul0 = q->g2cap;       /* dict col0 premultiplies via its dictmap */
+  }
+  if (plan->ngroup == 2 && q->gint[1]) dp.gbase[1] = q->gmin[1];
+  if (const Dim *jd = q->join_dim) {
+    dp.jkeys = jd->dev_keys;
+    dp.jpayload = jd->dev_payload;
+    dp.jcap_log2 = jd->cap_log2;
+    dp.jcslot = q->cslot_of_col[plan->join_fact_col];
+    dp.jmode = plan->join_mode == SN_JOIN_GROUP ? 1 : 0;
+    if (q->join_group && plan->ngroup >= 1)
+      dp.jslot_mul = q->fact_slots;   /* composite dim_attr x fact_col */
+    dp.jlut = jd->dev_lut;
+    dp.jlut_min = jd->lut_min;
+    dp.jlut_max = jd->lut_max;
+  }
+  int rc = build_preds(q, dp);
+  return rc != SN_OK ? rc : build_aggs(q, dp, dec);
+}
+
+/* the batch descriptors + tile map this plan scans.  Expensive at many
+ * batches (dict-map premultiply + uploads), so cached per plan signature; a
+ * cached set is only reusable when stats-skip removes nothing for THIS plan
+ * (skipping is an optimization — correctness is unaffected either way).  An
+ * uncacheable set's blocks belong to the query.  (The caller holds t->mu —
+ * same critical section as the slot derivation.) */
+static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out) {
+  sn_engine *e = q->e;
+  Table *t = q->t;
+  const sn_plan *plan = &q->plan;
   uint64_t sig = 1469598103934665603ull;
   auto mix = [&](uint64_t v) { sig ^= v; sig *= 1099511628211ull; };
   for (int32_t c : q->used_cols) mix((uint64_t)c + 1);
@@ -2437,18 +2461,22 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
   q->batches_seen = (int64_t)t->batches.size();
   q->batches_skipped = skip_count;
 
-  DescCache *hit = nullptr;
   if (skip_count == 0) {
     for (auto &dc : t->desc_caches)
-      if (dc.sig == sig && dc.batch_count == t->batches.size()) { hit = &dc; break; }
+      if (dc.sig == sig && dc.batch_count == t->batches.size()) {
+        *out = dc;
+        q->rows_scanned = dc.rows;
+        return SN_OK;
+      }
   }
 
+  ScanSet set;
+  set.sig = sig; set.batch_count = t->batches.size();
   std::vector<sn_dev_batch> hbatches;
   std::vector<sn_dev_tile> htiles;
   /* JIT eligibility: every unskipped batch clean, kinds uniform + stageable
-   * (derived here; stored in the DescCache for reuse on hits) */
-  bool jit_ok_b = true, jit_first = true, jit_any_del = false;
-  int jit_kinds[SN_DEV_MAX_COLS] = {0};
+   * (derived here; kept in the cached set for reuse on hits) */
+  bool jit_ok = true, jit_first = true;
   /* per-agg counts needed?  Only when a grouped plan's aggregate-input
    * columns carry ACTUAL nulls (null-free nullable schemas keep the
    * counts==rowcount fast layout, JIT included) */
@@ -2459,643 +2487,578 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
     if (A.nf >= 2) agg_cmask |= 1u << A.c1;
     if (A.nf >= 3) agg_cmask |= 1u << A.c2;
   }
-  bool agg_nulls = false;
+  const size_t nused = q->used_cols.size();
+  DictPremul pm[SN_DEV_MAX_COLS];
+  for (size_t ui = 0; ui < nused; ui++) pm[ui] = dict_premul(q, plan, q->used_cols[ui]);
   for (auto &b : t->batches) {
-    if (hit) break;
     if (skip_count && batch_skippable(b, plan, t)) continue;
     sn_dev_batch db;
     memset(&db, 0, sizeof(db));
     db.num_rows = b.num_rows;
     db.del_bm = b.del_bm_dev;
     bool clean = !b.has_deletes;
-    for (size_t ui = 0; ui < q->used_cols.size(); ui++) {
-      int c = q->used_cols[ui];
-      const ColMeta &m = b.cols[c];
-      sn_dev_col &dc = db.cols[ui];
-      memset(&dc, 0, sizeof(dc));
-      sn_type_t dt = t->schema[c].dtype;
-      dc.body = (const uint8_t *)b.col_dev[c] + m.body_off;
-      dc.has_nulls = m.num_null_words > 0;
-      if (dc.has_nulls) {
-        dc.nullw = (const uint64_t *)((const uint8_t *)b.col_dev[c] + m.null_off);
-        dc.nullpfx = b.nullpfx_dev[c];
-        clean = false;
-      }
-      switch (m.type_id) {
-        case SN_ENC_UNCOMPRESSED:
-          switch (dt) {
-            case SN_TYPE_DOUBLE: dc.kind = SN_K_F64; break;
-            case SN_TYPE_INT32: dc.kind = SN_K_I32; break;
-            case SN_TYPE_INT64: dc.kind = SN_K_I64; break;
-            case SN_TYPE_FLOAT: dc.kind = SN_K_F32; break;
-            case SN_TYPE_INT16: dc.kind = SN_K_I16; break;
-            case SN_TYPE_BOOL: dc.kind = SN_K_U8; break;
-            case SN_TYPE_INT8: dc.kind = SN_K_S8; break;
-            default:
-              fail(SN_ERR_UNSUPPORTED, "uncompressed %d on GPU path", (int)dt);
-              return nullptr;
-          }
-          break;
-        case SN_ENC_RUNLENGTH:
-          if (b.rle_n[c] <= 0 && b.num_rows > 0) {
-            fail(SN_ERR_UNSUPPORTED, "RLE col %d has no run aux", c);
-            return nullptr;
-          }
-          /* INT64 runs carry raw bits in rle_vals (put-time extraction) —
-           * a distinct kind so read_general bitcasts instead of rounding */
-          dc.kind = dt == SN_TYPE_INT64 ? SN_K_RLE_I64 : SN_K_RLE;
-          dc.rle_ends = b.rle_ends_dev[c];
-          dc.rle_vals = b.rle_vals_dev[c];
-          dc.rle_n = b.rle_n[c];
-          break;
-        case SN_ENC_BOOLEAN_BITSET:
-          dc.kind = SN_K_BOOLBIT;
-          break;
-        case SN_ENC_DICTIONARY:
-        case SN_ENC_BIG_DICTIONARY: {
-          if (dt != SN_TYPE_STRING) {
-            fail(SN_ERR_UNSUPPORTED, "int dictionary col on GPU path not yet supported");
-            return nullptr;
-          }
-          dc.kind = m.type_id == SN_ENC_DICTIONARY ? SN_K_DICT16 : SN_K_DICT32;
-          /* local->premultiplied-global map, cached per (mul, null_gid) —
-           * local2global is fixed per batch, so queries with the same
-           * group geometry reuse one device map */
-          bool is_g2 = plan->ngroup == 2 && plan->group_cols[1] == c;
-          int mul = is_g2 ? 1 : (q->g2cap > 0 ? q->g2cap : 1);
-          int gn = is_g2 ? q->gnull2 : q->gnull1;
-          int null_gid_local = gn >= 0 ? (is_g2 ? gn : gn * q->g2cap) : 0;
-          dc.null_gid = null_gid_local;
-          auto &mcache = b.dictmap_cache[c];
-          auto mit = mcache.find({ mul, null_gid_local });
-          if (mit != mcache.end()) {
-            dc.dictmap = mit->second;
-          } else {
-            std::vector<int32_t> map(m.local2global.size() + 1);
-            for (size_t i = 0; i < m.local2global.size(); i++)
-              map[i] = m.local2global[i] * mul;
-            /* index == numElements denotes null (DictionaryEncoding.scala:90) */
-            map[m.local2global.size()] = null_gid_local;
-            dc.dictmap = (const int32_t *)up(e, map.data(), map.size() * 4);
-            mcache.emplace(std::make_pair(mul, null_gid_local), dc.dictmap);
-          }
-          break;
-        }
-        default:
-          fail(SN_ERR_UNSUPPORTED, "encoding %d on GPU path not yet supported",
-               m.type_id);
-          return nullptr;
-      }
-      /* patches */
-      if (b.patch_dev[c].n > 0) {
-        clean = false;
-        const Batch::PatchDev &pd = b.patch_dev[c];
-        dc.patch_bm = pd.bm;
-        dc.patch_pos = pd.pos;
-        dc.patch_nullbm = pd.nullbm;
-        dc.patch_n = pd.n;
-        if (dt == SN_TYPE_STRING) {
-          /* premultiply global ids for this query */
-          bool is_g2 = plan->ngroup == 2 && plan->group_cols[1] == c;
-          int mul = is_g2 ? 1 : (q->g2cap > 0 ? q->g2cap : 1);
-          std::vector<double> pv(b.patch_host[c].val.size());
-          for (size_t i = 0; i < pv.size(); i++)
-            pv[i] = b.patch_host[c].val[i] * mul;
-          dc.patch_val = (const double *)up(e, pv.data(), pv.size() * 8);
-        } else {
-          dc.patch_val = pd.val;
-        }
-      }
+    for (size_t ui = 0; ui < nused; ui++) {
+      int rc = fill_dev_col(e, t, b, q->used_cols[ui], pm[ui].mul,
+                            pm[ui].null_gid, true, &db.cols[ui], &clean);
+      if (rc != SN_OK) return rc;
     }
     db.clean = clean ? 1 : 0;
-    for (size_t ui = 0; ui < q->used_cols.size(); ui++)
+    for (size_t ui = 0; ui < nused; ui++)
       if (((agg_cmask >> ui) & 1) &&
           (db.cols[ui].has_nulls || db.cols[ui].patch_nullbm))
-        agg_nulls = true;
+        set.pac = 1;
     /* deletes alone don't disqualify the JIT (the generated kernel reads
      * del_bm); nulls or unmaterialized patches on a used column do */
-    if (db.del_bm) jit_any_del = true;
-    for (size_t ui = 0; ui < q->used_cols.size() && jit_ok_b; ui++) {
+    if (db.del_bm) set.jit_del = 1;
+    for (size_t ui = 0; ui < nused && jit_ok; ui++) {
       const sn_dev_col &jc = db.cols[ui];
       int k = jc.kind;
       bool stageable = k == SN_K_F64 || k == SN_K_I64 || k == SN_K_I32 ||
                        k == SN_K_F32 || k == SN_K_I16 || k == SN_K_DICT16 ||
                        k == SN_K_DICT32;
-      if (!stageable || jc.has_nulls || jc.patch_n > 0) jit_ok_b = false;
-      else if (jit_first) jit_kinds[ui] = k;
-      else if (jit_kinds[ui] != k) jit_ok_b = false;
+      if (!stageable || jc.has_nulls || jc.patch_n > 0) jit_ok = false;
+      else if (jit_first) set.jit_kinds[ui] = k;
+      else if (set.jit_kinds[ui] != k) jit_ok = false;
     }
     jit_first = false;
     int32_t bi = (int32_t)hbatches.size();
     hbatches.push_back(db);
-    q->rows_scanned += b.num_rows;
+    set.rows += b.num_rows;
     for (int32_t r = 0; r < b.num_rows; r += SN_TILE_ROWS)
       htiles.push_back({ bi, r });
   }
+  set.jit_ok = (jit_ok && !jit_first) ? 1 : 0;
+  q->rows_scanned = set.rows;
 
-  /* upload + launch */
-  size_t out_n = (size_t)q->nslots * q->out_stride;
-  if (!q->sparse && !dec) {
-    q->dev_out = (double *)e->arena.alloc(out_n * 8);
-    if (!q->dev_out) { fail(SN_ERR_NOMEM, "out alloc"); return nullptr; }
-    q->owned.push_back({ q->dev_out, out_n * 8 });
-    if (hipMemsetAsync(q->dev_out, 0, out_n * 8, e->stream) != hipSuccess) {
-      fail(SN_ERR_GENERIC, "memset out"); return nullptr;
-    }
-  }
-  const void *db_dev = nullptr, *tl_dev = nullptr;
-  int32_t ntiles = 0;
-  if (hit) {
-    db_dev = hit->db_dev; tl_dev = hit->tl_dev;
-    ntiles = hit->ntiles;
-    q->rows_scanned = hit->rows;
-  } else if (!htiles.empty()) {
-    void *dbp = e->arena.alloc(hbatches.size() * sizeof(sn_dev_batch));
-    void *tlp = e->arena.alloc(htiles.size() * sizeof(sn_dev_tile));
-    if (!dbp || !tlp) { fail(SN_ERR_NOMEM, "desc alloc"); return nullptr; }
+  if (!htiles.empty()) {
+    set.db_bytes = hbatches.size() * sizeof(sn_dev_batch);
+    set.tl_bytes = htiles.size() * sizeof(sn_dev_tile);
+    void *dbp = e->arena.alloc(set.db_bytes);
+    void *tlp = e->arena.alloc(set.tl_bytes);
+    if (!dbp || !tlp) return fail(SN_ERR_NOMEM, "desc alloc");
     /* blocking copies: the host vectors are stack-local and die at return */
-    if (hipMemcpy(dbp, hbatches.data(), hbatches.size() * sizeof(sn_dev_batch),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(tlp, htiles.data(), htiles.size() * sizeof(sn_dev_tile),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-      fail(SN_ERR_GENERIC, "desc upload"); return nullptr;
-    }
-    db_dev = dbp; tl_dev = tlp;
-    ntiles = (int32_t)htiles.size();
+    if (hipMemcpy(dbp, hbatches.data(), set.db_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(tlp, htiles.data(), set.tl_bytes, hipMemcpyHostToDevice) != hipSuccess)
+      return fail(SN_ERR_GENERIC, "desc upload");
+    set.db_dev = dbp; set.tl_dev = tlp;
+    set.ntiles = (int32_t)htiles.size();
     if (skip_count != 0) {
       /* not cacheable (stats-skip removed batches): this query owns the
        * descriptor blocks; they recycle at sn_query_destroy */
-      q->owned.push_back({ dbp, hbatches.size() * sizeof(sn_dev_batch) });
-      q->owned.push_back({ tlp, htiles.size() * sizeof(sn_dev_tile) });
-    }
-    if (skip_count == 0) {
+      q->owned.push_back({ dbp, set.db_bytes });
+      q->owned.push_back({ tlp, set.tl_bytes });
+    } else {
       if (t->desc_caches.size() > 16) {
         /* evict the oldest cached set (FIFO); stream ordering guarantees
          * any in-flight kernel reading it finishes before a reuse write */
-        DescCache &old = t->desc_caches.front();
+        ScanSet &old = t->desc_caches.front();
         e->arena.release((void *)old.db_dev, old.db_bytes);
         e->arena.release((void *)old.tl_dev, old.tl_bytes);
         t->desc_caches.erase(t->desc_caches.begin());
       }
-      DescCache dc;
-      dc.sig = sig; dc.batch_count = t->batches.size();
-      dc.db_dev = db_dev; dc.tl_dev = tl_dev; dc.ntiles = ntiles;
-      dc.db_bytes = hbatches.size() * sizeof(sn_dev_batch);
-      dc.tl_bytes = htiles.size() * sizeof(sn_dev_tile);
-      dc.rows = q->rows_scanned;
-      dc.jit_ok = (jit_ok_b && !jit_first) ? 1 : 0;
-      dc.jit_del = jit_any_del ? 1 : 0;
-      memcpy(dc.jit_kinds, jit_kinds, sizeof(jit_kinds));
-      dc.pac = agg_nulls ? 1 : 0;
-      t->desc_caches.push_back(dc);
+      t->desc_caches.push_back(set);
     }
   }
-  {
-    /* MIN/MAX plans always take the pac layout (per-agg counts carry the
-     * empty-group NULL semantics; routing goes through the op-aware
-     * grouped kernels, keyless included) */
-    const bool grouped_mode = plan->ngroup > 0 || q->join_group;
-    q->pac = (grouped_mode && (hit ? hit->pac != 0 : agg_nulls)) || q->mm;
-    dp.pac = q->pac ? 1 : 0;
+  *out = set;
+  return SN_OK;
+}
+
+/* ---- launch helpers ---- */
+
+/* grid of a query-compiled scan: one block per tile up to the cap, then
+ * balanced rounds */
+static int jit_grid(int32_t ntiles) {
+  if (ntiles <= SN_GRID_CAP) return ntiles;
+  int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
+  return (ntiles + rounds - 1) / rounds;
+}
+
+/* IN-lists run compiled only in bitmap form (sorted-list search stays
+ * interpreted) */
+static bool jit_inlists_ok(const sn_dev_plan &dp) {
+  return dp.npreds_in == 0 ||
+         (dp.inp[0].bm && (dp.npreds_in < 2 || dp.inp[1].bm));
+}
+
+static void register_live(sn_engine *e, sn_query *q) {
+  std::lock_guard<std::mutex> ga(e->aux_mu);
+  e->live_q.insert(q);
+}
+
+/* grow the per-engine block-partial scratch to at least `need` bytes */
+static int32_t ensure_scratch(sn_engine *e, size_t need) {
+  if (e->scratch_sz >= need) return SN_OK;
+  e->scratch = (double *)e->arena.alloc(need);
+  e->scratch_sz = e->scratch ? need : 0;
+  return e->scratch ? SN_OK : fail(SN_ERR_NOMEM, "scratch alloc");
+}
+
+/* HIP events bracket the scan kernel on ITS stream for the roofline leg
+ * (torch.cuda.Event would only see torch's current stream) */
+static void acquire_events(sn_query *q) {
+  q->ev_start = q->e->ev_acquire();
+  q->ev_stop = q->e->ev_acquire();
+}
+
+/* ---- exact DECIMAL launch (k_dec_keyless / k_dec_grouped) ----
+ * canonical int64 factors, identical expressions deduped (Q1's sum/avg
+ * pairs share a device aggregate), COUNT(*) from the slot rowcount */
+static int32_t launch_decimal(sn_query *q, sn_dev_plan &dp, const ScanSet &set,
+                              const DecReq *dec) {
+  sn_engine *e = q->e;
+  const sn_plan *plan = &q->plan;
+  sn_dev_dec_plan ddp;
+  memset(&ddp, 0, sizeof(ddp));
+  int nd = 0;
+  for (int a = 0; a < dec->naggs; a++) {
+    const sn_dec_agg &sa = dec->aggs[a];
+    q->agg_map[a] = a;
+    if (sa.kind == SN_AGG_COUNT_STAR) { q->dec_map[a] = -1; continue; }
+    sn_dev_dec_agg da;
+    memset(&da, 0, sizeof(da));
+    da.op = sa.kind == SN_AGG_MIN ? 1 : sa.kind == SN_AGG_MAX ? 2 : 0;
+    da.nf = sa.nfactors;
+    for (int f = 0; f < 3; f++) {
+      if (f < sa.nfactors) {
+        da.c[f] = q->cslot_of_col[sa.factors[f].col];
+        da.add[f] = sa.factors[f].add;
+        da.mul[f] = sa.factors[f].mul;
+      } else {
+        da.c[f] = da.c[0]; da.add[f] = 1; da.mul[f] = 0;
+      }
+    }
+    int idx = -1;
+    for (int j = 0; j < nd; j++)
+      if (memcmp(&ddp.aggs[j], &da, sizeof(da)) == 0) { idx = j; break; }
+    if (idx < 0) { idx = nd; ddp.aggs[nd++] = da; }
+    q->dec_map[a] = idx;
   }
-  if (dec) {
-    /* ---- exact DECIMAL launch (k_dec_keyless / k_dec_grouped) ----
-     * canonical int64 factors, identical expressions deduped (Q1's sum/avg
-     * pairs share a device aggregate), COUNT(*) from the slot rowcount */
-    sn_dev_dec_plan ddp;
-    memset(&ddp, 0, sizeof(ddp));
-    int nd = 0;
-    for (int a = 0; a < dec->naggs; a++) {
-      const sn_dec_agg &sa = dec->aggs[a];
-      q->agg_map[a] = a;
-      if (sa.kind == SN_AGG_COUNT_STAR) { q->dec_map[a] = -1; continue; }
-      sn_dev_dec_agg da;
-      memset(&da, 0, sizeof(da));
-      da.op = sa.kind == SN_AGG_MIN ? 1 : sa.kind == SN_AGG_MAX ? 2 : 0;
-      da.nf = sa.nfactors;
-      for (int f = 0; f < 3; f++) {
-        if (f < sa.nfactors) {
-          da.c[f] = q->cslot_of_col[sa.factors[f].col];
-          da.add[f] = sa.factors[f].add;
-          da.mul[f] = sa.factors[f].mul;
-        } else {
-          da.c[f] = da.c[0]; da.add[f] = 1; da.mul[f] = 0;
-        }
-      }
-      int idx = -1;
-      for (int j = 0; j < nd; j++)
-        if (memcmp(&ddp.aggs[j], &da, sizeof(da)) == 0) { idx = j; break; }
-      if (idx < 0) { idx = nd; ddp.aggs[nd++] = da; }
-      q->dec_map[a] = idx;
-    }
-    ddp.naggs = nd;
-    q->dec_ndev = nd;
-    if (plan->ngroup == 0) q->nslots = 1;
-    if (plan->ngroup > 0 &&
-        q->nslots > sn_dec_max_slots(dp.nused, nd)) {
-      fail(SN_ERR_UNSUPPORTED,
-           "decimal group cardinality %d exceeds the %d-slot LDS accumulator "
-           "capacity for %d columns x %d aggregates",
-           q->nslots, sn_dec_max_slots(dp.nused, nd), dp.nused, nd);
-      return nullptr;
-    }
-    /* double view for sn_query_result: [sums naggs][counts naggs][rowcount] */
-    q->dec = true;
-    q->pac = true;
-    q->dev_naggs = plan->naggs;
-    q->na_t = plan->naggs;
-    q->out_stride = 2 * (size_t)plan->naggs + 1;
-    dp.nslots = q->nslots;
-    if (ntiles > 0) {
-      const size_t row_cells = (size_t)sn_dec_row_cells(nd);
-      const size_t outb = (size_t)q->nslots * row_cells * 8;
-      q->dec_out = (unsigned long long *)e->arena.alloc(outb);
-      if (!q->dec_out) { fail(SN_ERR_NOMEM, "decimal out alloc"); return nullptr; }
-      q->owned.push_back({ q->dec_out, outb });
-      const size_t planb = sizeof(dp) + sizeof(ddp);
-      uint8_t *plans_dev = (uint8_t *)e->arena.alloc(planb);
-      if (!plans_dev ||
-          hipMemcpy(plans_dev, &dp, sizeof(dp), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(plans_dev + sizeof(dp), &ddp, sizeof(ddp),
-                    hipMemcpyHostToDevice) != hipSuccess) {
-        fail(SN_ERR_NOMEM, "decimal plan upload"); return nullptr;
-      }
-      q->owned.push_back({ plans_dev, planb });
-      const size_t grid = (size_t)std::min<int32_t>(ntiles, SN_DEC_GRID_CAP);
-      const size_t need = grid * (size_t)q->nslots * row_cells * 8;
-      if (e->scratch_sz < need) {
-        e->scratch = (double *)e->arena.alloc(need);
-        e->scratch_sz = need;
-        if (!e->scratch) { e->scratch_sz = 0; fail(SN_ERR_NOMEM, "scratch alloc"); return nullptr; }
-      }
-      q->ev_start = e->ev_acquire();
-      q->ev_stop = e->ev_acquire();
-      if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
-      int rc = sn_launch_dec_scan(&dp, (const sn_dev_plan *)plans_dev, &ddp,
-                                  (const sn_dev_dec_plan *)(plans_dev + sizeof(dp)),
-                                  (const sn_dev_batch *)db_dev,
-                                  (const sn_dev_tile *)tl_dev, ntiles,
-                                  q->dec_out,
-                                  (unsigned long long *)e->scratch, e->stream);
-      if (q->ev_stop) (void)hipEventRecord(q->ev_stop, e->stream);
-      if (rc != 0) {
-        fail(SN_ERR_GENERIC, "decimal kernel launch: %s",
-             hipGetErrorString((hipError_t)rc));
-        return nullptr;
-      }
-    }
-    {
-      std::lock_guard<std::mutex> ga(e->aux_mu);
-      e->live_q.insert(q.get());
-    }
-    return q.release();
+  ddp.naggs = nd;
+  q->dec_ndev = nd;
+  if (plan->ngroup == 0) q->nslots = 1;
+  if (plan->ngroup > 0 && q->nslots > sn_dec_max_slots(dp.nused, nd))
+    return fail(SN_ERR_UNSUPPORTED,
+                "decimal group cardinality %d exceeds the %d-slot LDS accumulator "
+                "capacity for %d columns x %d aggregates",
+                q->nslots, sn_dec_max_slots(dp.nused, nd), dp.nused, nd);
+  /* double view for sn_query_result: [sums naggs][counts naggs][rowcount] */
+  q->dec = true;
+  q->pac = true;
+  q->dev_naggs = plan->naggs;
+  q->na_t = plan->naggs;
+  q->out_stride = 2 * (size_t)plan->naggs + 1;
+  dp.nslots = q->nslots;
+  if (set.ntiles == 0) return SN_OK;
+  const size_t row_cells = (size_t)sn_dec_row_cells(nd);
+  const size_t outb = (size_t)q->nslots * row_cells * 8;
+  q->dec_out = (unsigned long long *)e->arena.alloc(outb);
+  if (!q->dec_out) return fail(SN_ERR_NOMEM, "decimal out alloc");
+  q->owned.push_back({ q->dec_out, outb });
+  const size_t planb = sizeof(dp) + sizeof(ddp);
+  uint8_t *plans_dev = (uint8_t *)e->arena.alloc(planb);
+  if (!plans_dev ||
+      hipMemcpy(plans_dev, &dp, sizeof(dp), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(plans_dev + sizeof(dp), &ddp, sizeof(ddp),
+                hipMemcpyHostToDevice) != hipSuccess)
+    return fail(SN_ERR_NOMEM, "decimal plan upload");
+  q->owned.push_back({ plans_dev, planb });
+  const size_t grid = (size_t)std::min<int32_t>(set.ntiles, SN_DEC_GRID_CAP);
+  int rc = ensure_scratch(e, grid * (size_t)q->nslots * row_cells * 8);
+  if (rc != SN_OK) return rc;
+  acquire_events(q);
+  if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
+  rc = sn_launch_dec_scan(&dp, (const sn_dev_plan *)plans_dev, &ddp,
+                          (const sn_dev_dec_plan *)(plans_dev + sizeof(dp)),
+                          (const sn_dev_batch *)set.db_dev,
+                          (const sn_dev_tile *)set.tl_dev, set.ntiles,
+                          q->dec_out,
+                          (unsigned long long *)e->scratch, e->stream);
+  if (q->ev_stop) (void)hipEventRecord(q->ev_stop, e->stream);
+  if (rc != 0)
+    return fail(SN_ERR_GENERIC, "decimal kernel launch: %s",
+                hipGetErrorString((hipError_t)rc));
+  return SN_OK;
+}
+
+/* radix pass-1 buffers for one sparse attempt: grow the engine-cached record
+ * buffer and per-partition counters, point dps at them and zero the
+ * counters.  *radix goes false (single-pass probe instead) when the records
+ * would not fit. */
+static int32_t radix_prepare(sn_query *q, sn_dev_plan &dps, int cap_log2,
+                             int sub_log2, bool *radix) {
+  sn_engine *e = q->e;
+  const int npart = 1 << (cap_log2 - sub_log2);
+  const long long percap =
+      2 * q->rows_scanned / npart + 4096;
+  const size_t recb = (size_t)npart * (size_t)percap *
+                      (size_t)(1 + q->dev_naggs) * 8;
+  if (percap > INT32_MAX / 2 || recb > (48ull << 30)) {
+    *radix = false;
+    return SN_OK;
   }
-  if (q->sparse && ntiles > 0) {
-    /* ---- open-address hash-aggregate launch (k_grouped_hash) ----
-     * The workspace (key table + accumulators) is engine-cached; results
-     * are compacted on device and read back HERE (inside submit, stream
-     * synchronized), so concurrent queries never share the live table. */
-    const int naggs1 = (q->pac ? 2 : 1) * q->dev_naggs + 1;
-    /* capacity: 2x headroom over the worst-case distinct count keeps the
-     * linear probe short (load factor <= 0.5 at full distinctness); the
-     * fill counter grows the table before probing turns pathological,
-     * and the per-table hint skips the rediscovery next query */
-    int cap_log2 = 21;
-    while (cap_log2 > 12 && (1ll << (cap_log2 - 1)) >= 2 * q->rows_scanned)
-      cap_log2--;                      /* small tables: smaller table */
-    if (t->sparse_cap_hint > cap_log2) cap_log2 = t->sparse_cap_hint;
-    q->ev_start = e->ev_acquire();
-    q->ev_stop = e->ev_acquire();
-    /* radix two-pass: the single-pass probe touches ~3 random
-     * 64 B lines per row across a table far bigger than L2 (measured
-     * 182 B/row of HBM traffic on 1M keys).  For big tables the compiled
-     * pass 1 scatters (key, values) records into cap/4096 hash partitions
-     * (streaming traffic) and k_radix_agg aggregates each partition into
-     * its private L2-resident table segment.  JIT-only (clean batches);
-     * pac excluded (records carry values, not per-agg validity). */
-    static const bool radix_env = [] {
-      const char *v = getenv("SN_RADIX");
-      return !v || v[0] != '0';
-    }();
-    bool radix_ok = radix_env && !q->pac && q->dev_naggs <= 4;
-    bool done_h = false;
-    for (int attempt = 0; attempt < 4 && !done_h; attempt++) {
-      if (ensure_sparse_ws(e, cap_log2, naggs1) != SN_OK) {
-        fail(SN_ERR_NOMEM, "sparse hash workspace"); return nullptr;
-      }
-      const size_t cap = 1ull << cap_log2;
-      sn_dev_plan dps = dp;
-      dps.sparse = 1;
-      dps.hkeys = e->hws_keys;
-      dps.hacc = e->hws_acc;
-      dps.hflags = e->hws_flags;
-      dps.hcap_log2 = cap_log2;
-      bool radix = radix_ok && cap_log2 >= 17;
-      static const int sub_env = [] {      /* A/B lever for the sweep */
-        const char *v = getenv("SN_RADIX_SUB");
-        return v ? atoi(v) : 0;
-      }();
-      const int sub_log2 =
-          std::max(sub_env ? sub_env : SN_RADIX_SUB_MIN,
-                   cap_log2 - SN_RADIX_NPART_MAX_LOG2);
-      if (radix) {
-        const int npart = 1 << (cap_log2 - sub_log2);
-        const long long percap =
-            2 * q->rows_scanned / npart + 4096;
-        const size_t recb = (size_t)npart * (size_t)percap *
-                            (size_t)(1 + q->dev_naggs) * 8;
-        if (percap > INT32_MAX / 2 || recb > (48ull << 30)) {
-          radix = false;
-        } else {
-          if (!e->rws_recs || e->rws_bytes < recb) {
-            if (e->rws_recs) e->arena.release(e->rws_recs, e->rws_bytes);
-            e->rws_recs = (double *)e->arena.alloc(recb);
-            e->rws_bytes = e->rws_recs ? recb : 0;
-          }
-          if (e->rws_npart < npart) {
-            if (e->rws_pcount)
-              e->arena.release(e->rws_pcount, (size_t)e->rws_npart * 4);
-            e->rws_pcount = (int32_t *)e->arena.alloc((size_t)npart * 4);
-            e->rws_npart = e->rws_pcount ? npart : 0;
-          }
-          if (!e->rws_recs || !e->rws_pcount) {
-            radix = false;               /* fall back to the single pass */
-          } else {
-            dps.radix = sub_log2;
-            dps.precs = e->rws_recs;
-            dps.pcount = e->rws_pcount;
-            dps.percap = (int32_t)percap;
-            if (hipMemsetAsync(e->rws_pcount, 0, (size_t)npart * 4,
-                               e->stream) != hipSuccess) {
-              fail(SN_ERR_GENERIC, "radix counters zero"); return nullptr;
-            }
-          }
-        }
-      }
-      void *dps_dev = e->arena.alloc(sizeof(dps));
-      if (!dps_dev ||
-          hipMemcpy(dps_dev, &dps, sizeof(dps), hipMemcpyHostToDevice) != hipSuccess) {
-        fail(SN_ERR_NOMEM, "sparse plan upload"); return nullptr;
-      }
-      q->owned.push_back({ dps_dev, sizeof(dps) });
-      if (hipMemsetAsync(e->hws_keys, 0xff, cap * 8, e->stream) != hipSuccess ||
-          hipMemsetAsync(e->hws_acc, 0, (cap + 2) * (size_t)naggs1 * 8,
-                         e->stream) != hipSuccess ||
-          hipMemsetAsync(e->hws_flags, 0, 16, e->stream) != hipSuccess) {
-        fail(SN_ERR_GENERIC, "sparse workspace zero"); return nullptr;
-      }
-      if (q->mm &&
-          sn_launch_acc_init(e->hws_acc, (long long)cap + 2, q->dev_naggs,
-                             naggs1, dps_dev, e->stream) != 0) {
-        fail(SN_ERR_GENERIC, "sparse min/max init"); return nullptr;
-      }
-      /* query-compiled twin first (plan structure compile-time, capacity
-       * tokenized); any miss falls back to the interpreted hash kernel */
-      void *jfn = nullptr;
-      const bool jit_in_ok_s =
-          dp.npreds_in == 0 ||
-          (dp.inp[0].bm && (dp.npreds_in < 2 || dp.inp[1].bm));
-      if (e->jit && jit_in_ok_s && q->dev_naggs <= 12 &&
-          (hit ? hit->jit_ok != 0 : (jit_ok_b && !jit_first))) {
-        const int *jk = hit ? hit->jit_kinds : jit_kinds;
-        int jdel = hit ? hit->jit_del : (jit_any_del ? 1 : 0);
-        jfn = sn_jit_get(e->jit, &dps, jk, 0, q->na_t, jdel);
-      }
-      if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
-      int rc = -1;
-      if (jfn) {
-        int jgrid;
-        if (ntiles <= SN_GRID_CAP) jgrid = ntiles;
-        else {
-          int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
-          jgrid = (ntiles + rounds - 1) / rounds;
-        }
-        rc = sn_jit_launch(jfn, jgrid, (const sn_dev_batch *)db_dev,
-                           (const sn_dev_tile *)tl_dev, ntiles,
-                           e->hws_acc, (const int64_t *)e->hws_keys,
-                           (const int32_t *)e->hws_flags, nullptr,
-                           (const sn_dev_plan *)dps_dev, e->stream);
-        q->used_jit = rc == 0;
-        if (rc != 0) jfn = nullptr;
-      }
-      if (!jfn)
-        rc = sn_launch_hash_scan(&dps, (const sn_dev_plan *)dps_dev,
-                                 (const sn_dev_batch *)db_dev,
-                                 (const sn_dev_tile *)tl_dev, ntiles,
-                                 e->stream);
-      /* radix pass 2: aggregate the partitioned records (only meaningful
-       * after the compiled pass 1).  The LDS variant compacts straight
-       * into okeys/orows via the counter at hws_flags[1]. */
-      const bool radix_ran = radix && jfn;
-      const bool radix_direct = radix_ran && sn_radix_direct(sub_log2, naggs1);
-      if (rc == 0 && radix_ran)
-        rc = sn_launch_radix_agg(&dps, (const sn_dev_plan *)dps_dev,
-                                 e->hws_okeys, e->hws_orows,
-                                 (int *)(e->hws_flags + 1), e->stream);
-      if (q->ev_stop) (void)hipEventRecord(q->ev_stop, e->stream);
-      if (rc != 0) {
-        fail(SN_ERR_GENERIC, "hash-agg launch: %s",
-             hipGetErrorString((hipError_t)rc));
-        return nullptr;
-      }
-      if (hipStreamSynchronize(e->stream) != hipSuccess) {
-        fail(SN_ERR_GENERIC, "hash-agg sync"); return nullptr;
-      }
-      int32_t fl[4] = { 0, 0, 0, 0 };
-      (void)hipMemcpy(fl, e->hws_flags, 16, hipMemcpyDeviceToHost);
-      if (radix_ran && fl[3]) {
-        /* record buffer overflow (pathological key skew): redo this
-         * attempt through the single-pass probe — nothing was lost, the
-         * table is re-zeroed per attempt */
-        radix_ok = false;
-        attempt--;
-        continue;
-      }
-      const int32_t ovf = fl[0];
-      const int64_t fill = fl[2];
-      /* grow on hard overflow OR load factor > 0.6 (probe chains degrade
-       * sharply past that); results so far are correct either way */
-      if (ovf || (fill * 5 > (int64_t)cap * 3 && cap_log2 < 24)) {
-        if (ovf && cap_log2 >= 24) {
-          fail(SN_ERR_OVERFLOW,
-               "sparse group cardinality exceeds the 2^24 hash table");
-          return nullptr;
-        }
-        cap_log2 = std::min(cap_log2 + 2, 24);
-        continue;
-      }
-      t->sparse_cap_hint = std::max(t->sparse_cap_hint, cap_log2);
-      /* the LDS radix pass already compacted into okeys/orows (counter at
-       * hws_flags[1]); otherwise compact the table here */
-      if (!radix_direct &&
-          (hipMemsetAsync(e->hws_flags + 1, 0, 4, e->stream) != hipSuccess ||
-           sn_launch_hash_compact(e->hws_keys, e->hws_acc, (int)cap, naggs1,
-                                  e->hws_okeys, e->hws_orows,
-                                  (int *)(e->hws_flags + 1), e->stream) != 0 ||
-           hipStreamSynchronize(e->stream) != hipSuccess)) {
-        fail(SN_ERR_GENERIC, "hash-agg compact"); return nullptr;
-      }
-      int32_t ngrp = 0;
-      (void)hipMemcpy(&ngrp, e->hws_flags + 1, 4, hipMemcpyDeviceToHost);
-      /* the NULL-key group accumulates in the extra row at cap+1 (the
-       * compaction covers rows [0, cap]) */
-      q->sparse_null_row.assign((size_t)naggs1, 0.0);
-      (void)hipMemcpy(q->sparse_null_row.data(),
-                      e->hws_acc + (size_t)(cap + 1) * naggs1,
-                      (size_t)naggs1 * 8, hipMemcpyDeviceToHost);
-      q->sparse_keys.reset(new long long[(size_t)ngrp + 1]);
-      q->sparse_rows.reset(new double[((size_t)ngrp + 1) * naggs1]);
-      q->sparse_n = (size_t)ngrp;
-      if (ngrp > 0) {
-        /* plain pageable D2H: measured ~55 GB/s and stable once the heap
-         * recycles (mallopt in engine create) — the pinned bounce costs a
-         * second 24 MB host memcpy for nothing */
-        if (hipMemcpy(q->sparse_keys.get(), e->hws_okeys, (size_t)ngrp * 8,
-                      hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(q->sparse_rows.get(), e->hws_orows,
-                      (size_t)ngrp * naggs1 * 8,
-                      hipMemcpyDeviceToHost) != hipSuccess) {
-          fail(SN_ERR_GENERIC, "hash-agg readback"); return nullptr;
-        }
-      }
-      if (radix_direct) {
-        /* the LDS compaction never scans the (untouched) global table, so
-         * append the reserved sentinel-key row (a REAL key of -1) here —
-         * the same row k_hash_compact emits from index cap (the arrays
-         * were sized ngrp+1 for exactly this) */
-        double *rrow = q->sparse_rows.get() + q->sparse_n * naggs1;
-        (void)hipMemcpy(rrow, e->hws_acc + (size_t)cap * naggs1,
-                        (size_t)naggs1 * 8, hipMemcpyDeviceToHost);
-        if (rrow[naggs1 - 1] != 0.0) {
-          q->sparse_keys[q->sparse_n] = SN_HASH_EMPTY;
-          q->sparse_n++;
-        }
-      }
-      done_h = true;
-    }
-    {
-      std::lock_guard<std::mutex> ga(e->aux_mu);
-      e->live_q.insert(q.get());
-    }
-    return q.release();
+  if (!e->rws_recs || e->rws_bytes < recb) {
+    if (e->rws_recs) e->arena.release(e->rws_recs, e->rws_bytes);
+    e->rws_recs = (double *)e->arena.alloc(recb);
+    e->rws_bytes = e->rws_recs ? recb : 0;
   }
-  if (ntiles > 0) {
-    /* HIP events bracket the scan kernel on ITS stream for the roofline leg
-     * (torch.cuda.Event would only see torch's current stream) */
-    void *dp_dev = nullptr;
-    {
-      uint64_t dph = 1469598103934665603ull;
-      const uint8_t *db_ = (const uint8_t *)&dp;
-      for (size_t i = 0; i < sizeof(dp); i++) { dph ^= db_[i]; dph *= 1099511628211ull; }
-      std::lock_guard<std::mutex> ga(e->aux_mu);
-      auto it = e->dp_cache.find(dph);
-      if (it != e->dp_cache.end()) dp_dev = it->second;
-      else {
-        dp_dev = e->arena.alloc(sizeof(dp));
-        if (!dp_dev ||
-            hipMemcpy(dp_dev, &dp, sizeof(dp), hipMemcpyHostToDevice) != hipSuccess) {
-          fail(SN_ERR_NOMEM, "plan upload"); return nullptr;
-        }
-        if (e->dp_cache.size() > 64) {
-          for (auto &kv : e->dp_cache)
-            e->arena.release(kv.second, sizeof(sn_dev_plan));
-          e->dp_cache.clear();
-        }
-        e->dp_cache[dph] = dp_dev;
-      }
+  if (e->rws_npart < npart) {
+    if (e->rws_pcount)
+      e->arena.release(e->rws_pcount, (size_t)e->rws_npart * 4);
+    e->rws_pcount = (int32_t *)e->arena.alloc((size_t)npart * 4);
+    e->rws_npart = e->rws_pcount ? npart : 0;
+  }
+  if (!e->rws_recs || !e->rws_pcount) {
+    *radix = false;               /* fall back to the single pass */
+    return SN_OK;
+  }
+  dps.radix = sub_log2;
+  dps.precs = e->rws_recs;
+  dps.pcount = e->rws_pcount;
+  dps.percap = (int32_t)percap;
+  if (hipMemsetAsync(e->rws_pcount, 0, (size_t)npart * 4,
+                     e->stream) != hipSuccess)
+    return fail(SN_ERR_GENERIC, "radix counters zero");
+  return SN_OK;
+}
+
+/* compact the finished hash table on device (unless the LDS radix pass
+ * already did) and read the groups back into the query */
+static int32_t sparse_readback(sn_query *q, size_t cap, int naggs1,
+                               bool radix_direct) {
+  sn_engine *e = q->e;
+  /* the LDS radix pass already compacted into okeys/orows (counter at
+   * hws_flags[1]); otherwise compact the table here */
+  if (!radix_direct &&
+      (hipMemsetAsync(e->hws_flags + 1, 0, 4, e->stream) != hipSuccess ||
+       sn_launch_hash_compact(e->hws_keys, e->hws_acc, (int)cap, naggs1,
+                              e->hws_okeys, e->hws_orows,
+                              (int *)(e->hws_flags + 1), e->stream) != 0 ||
+       hipStreamSynchronize(e->stream) != hipSuccess))
+    return fail(SN_ERR_GENERIC, "hash-agg compact");
+  int32_t ngrp = 0;
+  (void)hipMemcpy(&ngrp, e->hws_flags + 1, 4, hipMemcpyDeviceToHost);
+  /* the NULL-key group accumulates in the extra row at cap+1 (the
+   * compaction covers rows [0, cap]) */
+  q->sparse_null_row.assign((size_t)naggs1, 0.0);
+  (void)hipMemcpy(q->sparse_null_row.data(),
+                  e->hws_acc + (size_t)(cap + 1) * naggs1,
+                  (size_t)naggs1 * 8, hipMemcpyDeviceToHost);
+  q->sparse_keys.reset(new long long[(size_t)ngrp + 1]);
+  q->sparse_rows.reset(new double[((size_t)ngrp + 1) * naggs1]);
+  q->sparse_n = (size_t)ngrp;
+  if (ngrp > 0) {
+    /* plain pageable D2H: measured ~55 GB/s and stable once the heap
+     * recycles (mallopt in engine create) — the pinned bounce costs a
+     * second 24 MB host memcpy for nothing */
+    if (hipMemcpy(q->sparse_keys.get(), e->hws_okeys, (size_t)ngrp * 8,
+                  hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(q->sparse_rows.get(), e->hws_orows,
+                  (size_t)ngrp * naggs1 * 8,
+                  hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(SN_ERR_GENERIC, "hash-agg readback");
+  }
+  if (radix_direct) {
+    /* the LDS compaction never scans the (untouched) global table, so
+     * append the reserved sentinel-key row (a REAL key of -1) here —
+     * the same row k_hash_compact emits from index cap (the arrays
+     * were sized ngrp+1 for exactly this) */
+    double *rrow = q->sparse_rows.get() + q->sparse_n * naggs1;
+    (void)hipMemcpy(rrow, e->hws_acc + (size_t)cap * naggs1,
+                    (size_t)naggs1 * 8, hipMemcpyDeviceToHost);
+    if (rrow[naggs1 - 1] != 0.0) {
+      q->sparse_keys[q->sparse_n] = SN_HASH_EMPTY;
+      q->sparse_n++;
     }
-    /* block-partial scratch rows (the >16-slot path caps its grid) */
-    int grid = ntiles < SN_GRID_CAP ? ntiles : SN_GRID_CAP;
-    if (dp.nslots > 16 && grid > SN_GRID_BIGSLOT) grid = SN_GRID_BIGSLOT;
-    const int na1 = dp.pac ? 2 * q->dev_naggs + 1 : q->dev_naggs + 1;
-    size_t nv = (dp.nslots <= 1 && !dp.pac)
-                    ? (size_t)(2 * q->na_t + 1)
-                    : (size_t)(dp.nslots < 1 ? 1 : dp.nslots) * na1;
-    const bool big_groups =
-        dp.nslots > SN_RESULT_PAGE ||
-        (dp.pac && sn_grouped_needs_global(dp.nused, dp.nslots, na1));
-    size_t need = (big_groups ? 8 : (size_t)grid) * nv * 8;
-    if (e->scratch_sz < need) {
-      e->scratch = (double *)e->arena.alloc(need);
-      e->scratch_sz = need;
-      if (!e->scratch) { fail(SN_ERR_NOMEM, "scratch alloc"); return nullptr; }
+  }
+  return SN_OK;
+}
+
+/* ---- open-address hash-aggregate launch (k_grouped_hash) ----
+ * The workspace (key table + accumulators) is engine-cached; results
+ * are compacted on device and read back HERE (inside submit, stream
+ * synchronized), so concurrent queries never share the live table. */
+static int32_t launch_sparse(sn_query *q, const sn_dev_plan &dp,
+                             const ScanSet &set) {
+  sn_engine *e = q->e;
+  Table *t = q->t;
+  if (set.ntiles == 0) return SN_OK;
+  const int naggs1 = (q->pac ? 2 : 1) * q->dev_naggs + 1;
+  /* capacity: 2x headroom over the worst-case distinct count keeps the
+   * linear probe short (load factor <= 0.5 at full distinctness); the
+   * fill counter grows the table before probing turns pathological,
+   * and the per-table hint skips the rediscovery next query */
+  int cap_log2 = 21;
+  while (cap_log2 > 12 && (1ll << (cap_log2 - 1)) >= 2 * q->rows_scanned)
+    cap_log2--;                      /* small tables: smaller table */
+  if (t->sparse_cap_hint > cap_log2) cap_log2 = t->sparse_cap_hint;
+  acquire_events(q);
+  /* radix two-pass: the single-pass probe touches ~3 random
+   * 64 B lines per row across a table far bigger than L2 (measured
+   * 182 B/row of HBM traffic on 1M keys).  For big tables the compiled
+   * pass 1 scatters (key, values) records into cap/4096 hash partitions
+   * (streaming traffic) and k_radix_agg aggregates each partition into
+   * its private L2-resident table segment.  JIT-only (clean batches);
+   * pac excluded (records carry values, not per-agg validity). */
+  static const bool radix_env = [] {
+    const char *v = getenv("SN_RADIX");
+    return !v || v[0] != '0';
+  }();
+  static const int sub_env = [] {      /* A/B lever for the sweep */
+    const char *v = getenv("SN_RADIX_SUB");
+    return v ? atoi(v) : 0;
+  }();
+  bool radix_ok = radix_env && !q->pac && q->dev_naggs <= 4;
+  bool done_h = false;
+  for (int attempt = 0; attempt < 4 && !done_h; attempt++) {
+    if (ensure_sparse_ws(e, cap_log2, naggs1) != SN_OK)
+      return fail(SN_ERR_NOMEM, "sparse hash workspace");
+    const size_t cap = 1ull << cap_log2;
+    sn_dev_plan dps = dp;
+    dps.sparse = 1;
+    dps.hkeys = e->hws_keys;
+    dps.hacc = e->hws_acc;
+    dps.hflags = e->hws_flags;
+    dps.hcap_log2 = cap_log2;
+    bool radix = radix_ok && cap_log2 >= 17;
+    const int sub_log2 =
+        std::max(sub_env ? sub_env : SN_RADIX_SUB_MIN,
+                 cap_log2 - SN_RADIX_NPART_MAX_LOG2);
+    if (radix) {
+      int rc = radix_prepare(q, dps, cap_log2, sub_log2, &radix);
+      if (rc != SN_OK) return rc;
     }
-    if (big_groups &&
-        hipMemsetAsync(e->scratch, 0, 8 * nv * 8, e->stream) != hipSuccess) {
-      fail(SN_ERR_GENERIC, "accumulator zero"); return nullptr;
-    }
-    if (big_groups && q->mm &&
-        sn_launch_acc_init(e->scratch, 8ll * dp.nslots, q->dev_naggs, na1,
-                           dp_dev, e->stream) != 0) {
-      fail(SN_ERR_GENERIC, "accumulator min/max init"); return nullptr;
-    }
-    q->ev_start = e->ev_acquire();
-    q->ev_stop = e->ev_acquire();
-    /* query-compiled kernel (jit.cpp): plan constants baked as literals —
-     * the WholeStageCodegen analogue; measured 3x on Q1's shape over the
-     * interpreted runtime-plan kernel.  Any miss falls back, still on GPU. */
+    const void *dps_dev = up_owned(q, &dps, sizeof(dps));
+    if (!dps_dev) return fail(SN_ERR_NOMEM, "sparse plan upload");
+    if (hipMemsetAsync(e->hws_keys, 0xff, cap * 8, e->stream) != hipSuccess ||
+        hipMemsetAsync(e->hws_acc, 0, (cap + 2) * (size_t)naggs1 * 8,
+                       e->stream) != hipSuccess ||
+        hipMemsetAsync(e->hws_flags, 0, 16, e->stream) != hipSuccess)
+      return fail(SN_ERR_GENERIC, "sparse workspace zero");
+    if (q->mm &&
+        sn_launch_acc_init(e->hws_acc, (long long)cap + 2, q->dev_naggs,
+                           naggs1, dps_dev, e->stream) != 0)
+      return fail(SN_ERR_GENERIC, "sparse min/max init");
+    /* query-compiled twin first (plan structure compile-time, capacity
+     * tokenized); any miss falls back to the interpreted hash kernel */
     void *jfn = nullptr;
-    bool jit_shape_ok;
-    if (dp.nslots <= 1 && !dp.pac) jit_shape_ok = dp.naggs <= 12;
-    else if (dp.nslots <= 8) jit_shape_ok = dp.naggs <= 6;
-    else if (dp.nslots <= 1024)
-      /* LDS-accumulator mode: static shared = LDS image + gacc must fit */
-      jit_shape_ok = (size_t)dp.nused * 8192 +
-                     (size_t)dp.nslots * na1 * 8 + 1024 <= 160 * 1024;
-    else
-      /* global-atomic mode: only the LDS image constrains */
-      jit_shape_ok = dp.nslots <= SN_BIG_GROUP_CAP;
-    /* pac from ACTUAL nulls never reaches here (jit_ok excludes null
-     * batches); pac from MIN/MAX compiles op-aware kernels.  IN-lists run
-     * compiled only in bitmap form (sorted-list search stays interpreted). */
-    const bool jit_in_ok =
-        dp.npreds_in == 0 ||
-        (dp.inp[0].bm && (dp.npreds_in < 2 || dp.inp[1].bm));
-    if (e->jit && jit_shape_ok && jit_in_ok &&
-        (hit ? hit->jit_ok != 0 : (jit_ok_b && !jit_first))) {
-      const int *jk = hit ? hit->jit_kinds : jit_kinds;
-      int jdel = hit ? hit->jit_del : (jit_any_del ? 1 : 0);
-      jfn = sn_jit_get(e->jit, &dp, jk, dp.nslots, q->na_t, jdel);
-    }
+    if (e->jit && jit_inlists_ok(dp) && q->dev_naggs <= 12 && set.jit_ok)
+      jfn = sn_jit_get(e->jit, &dps, set.jit_kinds, 0, q->na_t, set.jit_del);
     if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
     int rc = -1;
     if (jfn) {
-      int jgrid;
-      if (ntiles <= SN_GRID_CAP) jgrid = ntiles;
-      else {
-        int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
-        jgrid = (ntiles + rounds - 1) / rounds;
-      }
-      /* >16-slot scratch rows are wide; mirror the interpreted grid cap
-       * (scratch was sized with the same bound above) */
-      if (dp.nslots > 16 && jgrid > SN_GRID_BIGSLOT) jgrid = SN_GRID_BIGSLOT;
-      int naggs1 = (dp.nslots <= 1 && !dp.pac) ? 0 : na1;
-      rc = sn_jit_launch(jfn, jgrid, (const sn_dev_batch *)db_dev,
-                         (const sn_dev_tile *)tl_dev, ntiles, e->scratch,
-                         dp.jkeys, dp.jpayload, dp.jlut,
-                         (const sn_dev_plan *)dp_dev, e->stream);
-      if (rc == 0)
-        rc = sn_launch_reduce(e->scratch, big_groups ? 8 : jgrid, (int)nv,
-                              q->dev_out, naggs1, (int)q->out_stride,
-                              dp_dev, e->stream);
+      rc = sn_jit_launch(jfn, jit_grid(set.ntiles),
+                         (const sn_dev_batch *)set.db_dev,
+                         (const sn_dev_tile *)set.tl_dev, set.ntiles,
+                         e->hws_acc, (const int64_t *)e->hws_keys,
+                         (const int32_t *)e->hws_flags, nullptr,
+                         (const sn_dev_plan *)dps_dev, e->stream);
       q->used_jit = rc == 0;
-      if (rc != 0) jfn = nullptr;   /* interpreted kernels take over */
+      if (rc != 0) jfn = nullptr;
     }
     if (!jfn)
-      rc = sn_launch_scan_agg(&dp, (const sn_dev_plan *)dp_dev,
-                              (const sn_dev_batch *)db_dev,
-                              (const sn_dev_tile *)tl_dev, ntiles,
-                              q->dev_out, e->scratch, e->stream);
+      rc = sn_launch_hash_scan(&dps, (const sn_dev_plan *)dps_dev,
+                               (const sn_dev_batch *)set.db_dev,
+                               (const sn_dev_tile *)set.tl_dev, set.ntiles,
+                               e->stream);
+    /* radix pass 2: aggregate the partitioned records (only meaningful
+     * after the compiled pass 1).  The LDS variant compacts straight
+     * into okeys/orows via the counter at hws_flags[1]. */
+    const bool radix_ran = radix && jfn;
+    const bool radix_direct = radix_ran && sn_radix_direct(sub_log2, naggs1);
+    if (rc == 0 && radix_ran)
+      rc = sn_launch_radix_agg(&dps, (const sn_dev_plan *)dps_dev,
+                               e->hws_okeys, e->hws_orows,
+                               (int *)(e->hws_flags + 1), e->stream);
     if (q->ev_stop) (void)hipEventRecord(q->ev_stop, e->stream);
-    if (rc != 0) {
-      fail(SN_ERR_GENERIC, "kernel launch: %s", hipGetErrorString((hipError_t)rc));
-      return nullptr;
+    if (rc != 0)
+      return fail(SN_ERR_GENERIC, "hash-agg launch: %s",
+                  hipGetErrorString((hipError_t)rc));
+    if (hipStreamSynchronize(e->stream) != hipSuccess)
+      return fail(SN_ERR_GENERIC, "hash-agg sync");
+    int32_t fl[4] = { 0, 0, 0, 0 };
+    (void)hipMemcpy(fl, e->hws_flags, 16, hipMemcpyDeviceToHost);
+    if (radix_ran && fl[3]) {
+      /* record buffer overflow (pathological key skew): redo this
+       * attempt through the single-pass probe — nothing was lost, the
+       * table is re-zeroed per attempt */
+      radix_ok = false;
+      attempt--;
+      continue;
     }
+    const int32_t ovf = fl[0];
+    const int64_t fill = fl[2];
+    /* grow on hard overflow OR load factor > 0.6 (probe chains degrade
+     * sharply past that); results so far are correct either way */
+    if (ovf || (fill * 5 > (int64_t)cap * 3 && cap_log2 < 24)) {
+      if (ovf && cap_log2 >= 24)
+        return fail(SN_ERR_OVERFLOW,
+                    "sparse group cardinality exceeds the 2^24 hash table");
+      cap_log2 = std::min(cap_log2 + 2, 24);
+      continue;
+    }
+    t->sparse_cap_hint = std::max(t->sparse_cap_hint, cap_log2);
+    rc = sparse_readback(q, cap, naggs1, radix_direct);
+    if (rc != SN_OK) return rc;
+    done_h = true;
   }
-  {
-    std::lock_guard<std::mutex> ga(e->aux_mu);
-    e->live_q.insert(q.get());
+  return SN_OK;
+}
+
+/* device copy of a dense-path plan, cached per engine by content hash */
+static void *cached_dev_plan(sn_engine *e, const sn_dev_plan &dp) {
+  uint64_t dph = 1469598103934665603ull;
+  const uint8_t *db_ = (const uint8_t *)&dp;
+  for (size_t i = 0; i < sizeof(dp); i++) { dph ^= db_[i]; dph *= 1099511628211ull; }
+  std::lock_guard<std::mutex> ga(e->aux_mu);
+  auto it = e->dp_cache.find(dph);
+  if (it != e->dp_cache.end()) return it->second;
+  void *dp_dev = e->arena.alloc(sizeof(dp));
+  if (!dp_dev ||
+      hipMemcpy(dp_dev, &dp, sizeof(dp), hipMemcpyHostToDevice) != hipSuccess)
+    return nullptr;
+  if (e->dp_cache.size() > 64) {
+    for (auto &kv : e->dp_cache)
+      e->arena.release(kv.second, sizeof(sn_dev_plan));
+    e->dp_cache.clear();
   }
+  e->dp_cache[dph] = dp_dev;
+  return dp_dev;
+}
+
+/* ---- dense launch: keyless or direct-slot grouped (k_scan_agg family or
+ * its query-compiled twin) into a per-query result buffer ---- */
+static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
+                            const ScanSet &set) {
+  sn_engine *e = q->e;
+  const int32_t ntiles = set.ntiles;
+  size_t out_n = (size_t)q->nslots * q->out_stride;
+  q->dev_out = (double *)e->arena.alloc(out_n * 8);
+  if (!q->dev_out) return fail(SN_ERR_NOMEM, "out alloc");
+  q->owned.push_back({ q->dev_out, out_n * 8 });
+  if (hipMemsetAsync(q->dev_out, 0, out_n * 8, e->stream) != hipSuccess)
+    return fail(SN_ERR_GENERIC, "memset out");
+  if (ntiles == 0) return SN_OK;
+  void *dp_dev = cached_dev_plan(e, dp);
+  if (!dp_dev) return fail(SN_ERR_NOMEM, "plan upload");
+  /* block-partial scratch rows (the >16-slot path caps its grid) */
+  int grid = ntiles < SN_GRID_CAP ? ntiles : SN_GRID_CAP;
+  if (dp.nslots > 16 && grid > SN_GRID_BIGSLOT) grid = SN_GRID_BIGSLOT;
+  const int na1 = dp.pac ? 2 * q->dev_naggs + 1 : q->dev_naggs + 1;
+  size_t nv = (dp.nslots <= 1 && !dp.pac)
+                  ? (size_t)(2 * q->na_t + 1)
+                  : (size_t)(dp.nslots < 1 ? 1 : dp.nslots) * na1;
+  const bool big_groups =
+      dp.nslots > SN_RESULT_PAGE ||
+      (dp.pac && sn_grouped_needs_global(dp.nused, dp.nslots, na1));
+  int rc = ensure_scratch(e, (big_groups ? 8 : (size_t)grid) * nv * 8);
+  if (rc != SN_OK) return rc;
+  if (big_groups &&
+      hipMemsetAsync(e->scratch, 0, 8 * nv * 8, e->stream) != hipSuccess)
+    return fail(SN_ERR_GENERIC, "accumulator zero");
+  if (big_groups && q->mm &&
+      sn_launch_acc_init(e->scratch, 8ll * dp.nslots, q->dev_naggs, na1,
+                         dp_dev, e->stream) != 0)
+    return fail(SN_ERR_GENERIC, "accumulator min/max init");
+  acquire_events(q);
+  /* query-compiled kernel (jit.cpp): plan constants baked as literals —
+   * the WholeStageCodegen analogue; measured 3x on Q1's shape over the
+   * interpreted runtime-plan kernel.  Any miss falls back, still on GPU. */
+  void *jfn = nullptr;
+  bool jit_shape_ok;
+  if (dp.nslots <= 1 && !dp.pac) jit_shape_ok = dp.naggs <= 12;
+  else if (dp.nslots <= 8) jit_shape_ok = dp.naggs <= 6;
+  else if (dp.nslots <= 1024)
+    /* LDS-accumulator mode: static shared = LDS image + gacc must fit */
+    jit_shape_ok = (size_t)dp.nused * 8192 +
+                   (size_t)dp.nslots * na1 * 8 + 1024 <= 160 * 1024;
+  else
+    /* global-atomic mode: only the LDS image constrains */
+    jit_shape_ok = dp.nslots <= SN_BIG_GROUP_CAP;
+  /* pac from ACTUAL nulls never reaches here (jit_ok excludes null
+   * batches); pac from MIN/MAX compiles op-aware kernels. */
+  if (e->jit && jit_shape_ok && jit_inlists_ok(dp) && set.jit_ok)
+    jfn = sn_jit_get(e->jit, &dp, set.jit_kinds, dp.nslots, q->na_t, set.jit_del);
+  if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
+  rc = -1;
+  if (jfn) {
+    int jgrid = jit_grid(ntiles);
+    /* >16-slot scratch rows are wide; mirror the interpreted grid cap
+     * (scratch was sized with the same bound above) */
+    if (dp.nslots > 16 && jgrid > SN_GRID_BIGSLOT) jgrid = SN_GRID_BIGSLOT;
+    int naggs1 = (dp.nslots <= 1 && !dp.pac) ? 0 : na1;
+    rc = sn_jit_launch(jfn, jgrid, (const sn_dev_batch *)set.db_dev,
+                       (const sn_dev_tile *)set.tl_dev, ntiles, e->scratch,
+                       dp.jkeys, dp.jpayload, dp.jlut,
+                       (const sn_dev_plan *)dp_dev, e->stream);
+    if (rc == 0)
+      rc = sn_launch_reduce(e->scratch, big_groups ? 8 : jgrid, (int)nv,
+                            q->dev_out, naggs1, (int)q->out_stride,
+                            dp_dev, e->stream);
+    q->used_jit = rc == 0;
+    if (rc != 0) jfn = nullptr;   /* interpreted kernels take over */
+  }
+  if (!jfn)
+    rc = sn_launch_scan_agg(&dp, (const sn_dev_plan *)dp_dev,
+                            (const sn_dev_batch *)set.db_dev,
+                            (const sn_dev_tile *)set.tl_dev, ntiles,
+                            q->dev_out, e->scratch, e->stream);
+  if (q->ev_stop) (void)hipEventRecord(q->ev_stop, e->stream);
+  if (rc != 0)
+    return fail(SN_ERR_GENERIC, "kernel launch: %s", hipGetErrorString((hipError_t)rc));
+  return SN_OK;
+}
+
+/* shared submit body: a short orchestrator over the phases above, in an
+ * order that decides which check of a bad plan fails first.  dec == NULL is
+ * sn_query_submit; otherwise `plan` carries a double-typed image of the
+ * decimal aggregates (so column collection, slot derivation, descriptor
+ * build and stats skipping are the double path's own code) and the launch
+ * routes to the exact decimal kernels. */
+static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
+                             const DecReq *dec) {
+  if (!e || !plan) { fail(SN_ERR_BADARG, "null engine/plan"); return nullptr; }
+  Table *t = get_table(e, plan->table);
+  if (!t) { fail(SN_ERR_BADARG, "unknown table %d", plan->table); return nullptr; }
+  if (!e->has_gpu) { fail(SN_ERR_NOGPU, "no HIP device — the engine never falls back to CPU"); return nullptr; }
+  /* one submit at a time per engine (shared stream/scratch/workspaces) */
+  std::lock_guard<std::mutex> qg(e->query_mu);
+  if (plan->npreds > SN_MAX_PREDS || plan->naggs > SN_MAX_AGGS ||
+      plan->ngroup > SN_MAX_GROUPS || plan->naggs <= 0) {
+    fail(SN_ERR_BADARG, "plan limits exceeded"); return nullptr;
+  }
+
+  auto q = std::make_unique<sn_query>();
+  q->e = e; q->t = t; q->plan = *plan;
+  if (collect_plan_columns(q.get()) != SN_OK) return nullptr;
+  if (resolve_join(q.get()) != SN_OK) return nullptr;
+
+  /* ONE t->mu critical section from group-slot derivation through the
+   * descriptor build below: a concurrent sn_batch_put (config-5
+   * ingest+scan) may grow the global dictionary and append batches; slot
+   * capacities, premultiplied dictmaps and the descriptor set must all see
+   * the same consistent table state or grouped kernels write accumulator
+   * rows out of bounds.  Held to return: the sparse launch synchronizes
+   * and reads back under it too. */
+  std::lock_guard<std::mutex> g(t->mu);
+  sync_pending_stats(e, t);   /* raw-ingested batches: resolve device bounds */
+
+  if (derive_group_slots(q.get(), dec != nullptr) != SN_OK) return nullptr;
+  sn_dev_plan dp;
+  if (build_dev_plan(q.get(), dec != nullptr, dp) != SN_OK) return nullptr;
+  ScanSet set;
+  if (resolve_scan_set(q.get(), dp, &set) != SN_OK) return nullptr;
+  /* MIN/MAX plans always take the pac layout (per-agg counts carry the
+   * empty-group NULL semantics; routing goes through the op-aware
+   * grouped kernels, keyless included) */
+  const bool grouped_mode = plan->ngroup > 0 || q->join_group;
+  q->pac = (grouped_mode && set.pac) || q->mm;
+  dp.pac = q->pac ? 1 : 0;
+
+  int32_t rc = dec         ? launch_decimal(q.get(), dp, set, dec)
+               : q->sparse ? launch_sparse(q.get(), dp, set)
+                           : launch_dense(q.get(), dp, set);
+  if (rc != SN_OK) return nullptr;
+  register_live(e, q.get());
   return q.release();
 }
 
