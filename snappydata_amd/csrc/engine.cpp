@@ -2841,7 +2841,7 @@ static int32_t launch_sparse(sn_query *q, const sn_dev_plan &dp,
     /* query-compiled twin first (plan structure compile-time, capacity
      * tokenized); any miss falls back to the interpreted hash kernel */
     void *jfn = nullptr;
-    if (e->jit && jit_inlists_ok(dp) && q->dev_naggs <= 12 && set.jit_ok)
+    if (e->jit && jit_inlists_ok(dp) && sn_jit_shape_ok(&dps) && set.jit_ok)
       jfn = sn_jit_get(e->jit, &dps, set.jit_kinds, 0, q->na_t, set.jit_del);
     if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
     int rc = -1;
@@ -2964,19 +2964,9 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
    * the WholeStageCodegen analogue; measured 3x on Q1's shape over the
    * interpreted runtime-plan kernel.  Any miss falls back, still on GPU. */
   void *jfn = nullptr;
-  bool jit_shape_ok;
-  if (dp.nslots <= 1 && !dp.pac) jit_shape_ok = dp.naggs <= 12;
-  else if (dp.nslots <= 8) jit_shape_ok = dp.naggs <= 6;
-  else if (dp.nslots <= 1024)
-    /* LDS-accumulator mode: static shared = LDS image + gacc must fit */
-    jit_shape_ok = (size_t)dp.nused * 8192 +
-                   (size_t)dp.nslots * na1 * 8 + 1024 <= 160 * 1024;
-  else
-    /* global-atomic mode: only the LDS image constrains */
-    jit_shape_ok = dp.nslots <= SN_BIG_GROUP_CAP;
   /* pac from ACTUAL nulls never reaches here (jit_ok excludes null
    * batches); pac from MIN/MAX compiles op-aware kernels. */
-  if (e->jit && jit_shape_ok && jit_inlists_ok(dp) && set.jit_ok)
+  if (e->jit && sn_jit_shape_ok(&dp) && jit_inlists_ok(dp) && set.jit_ok)
     jfn = sn_jit_get(e->jit, &dp, set.jit_kinds, dp.nslots, q->na_t, set.jit_del);
   if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
   rc = -1;
@@ -3457,12 +3447,6 @@ static void local_groups(sn_query *q, std::vector<GroupOut> *out) {
       if (p.ngroup == 0 && !q->join_group) {
         /* keyless MIN/MAX plans run the grouped (pac) layout with 1 slot:
          * counts land at [naggs + a] instead of the keyless [na_t + a] */
-        if (a == 0 && getenv("SN_DBG")) {
-          fprintf(stderr, "[dbg] pac=%d dev_naggs=%d na_t=%d p.naggs=%d stride=%d row=",
-                  q->pac ? 1 : 0, q->dev_naggs, q->na_t, p.naggs, (int)q->out_stride);
-          for (size_t i = 0; i < q->out_stride; i++) fprintf(stderr, "%g ", row[i]);
-          fprintf(stderr, "\n");
-        }
         g.sums[a] = row[a];
         g.counts[a] = q->pac ? row[p.naggs + a] : row[q->na_t + a];
       } else {

@@ -399,6 +399,11 @@ int sn_launch_acc_init(double *acc, long long rows, int naggs, int na1,
 /* query-compiled scan kernels (jit.cpp, hipRTC).  sn_jit_get returns an
  * opaque hipFunction_t for the plan (compiling + caching on first use) or
  * NULL -> caller falls back to the interpreted kernels. */
+/* does a plan of this shape (nused, nslots, naggs, pac, sparse) fit a
+ * query-compiled kernel?  The slot, aggregate and LDS limits live next to
+ * the generator's mode classifier, so the host's routing and the generated
+ * kernel can never disagree. */
+int sn_jit_shape_ok(const sn_dev_plan *p);
 void *sn_jit_cache_create(void);
 void sn_jit_cache_destroy(void *cache);
 int sn_jit_cache_count(void *cache);

@@ -19,11 +19,17 @@
  * aggregate coefficients are tokenized (read from the cached device plan
  * at run time), so different literal values of the same shape reuse one
  * compiled kernel — the reference's ParamLiteral tokenization.
+ *
+ * Layout of this file: the shape classifier (JitShape: which accumulator,
+ * join-probe and slot scheme a plan gets, and the limits the engine asks
+ * about), the column-kind table, one emitter per piece of the kernel, and
+ * gen_source, which strings the emitters together in kernel order.
  */
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -53,46 +59,294 @@ extern "C" void sn_jit_cache_destroy(void *c) {
   delete jc;
 }
 
-static void emitf(std::string &o, const char *fmt, ...) {
-  char buf[1024];
-  va_list ap; va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
+/* printf into a string: sized by a first pass, so no line can truncate */
+__attribute__((format(printf, 1, 2)))
+static std::string strf(const char *fmt, ...) {
+  va_list ap, ap2;
+  va_start(ap, fmt);
+  va_copy(ap2, ap);
+  const int n = vsnprintf(nullptr, 0, fmt, ap);
   va_end(ap);
-  o += buf;
+  std::string s(n > 0 ? (size_t)n + 1 : 0, '\0');
+  if (n > 0) vsnprintf(&s[0], s.size(), fmt, ap2), s.resize((size_t)n);
+  va_end(ap2);
+  return s;
 }
+#define emitf(o, ...) ((o) += strf(__VA_ARGS__))
 
-/* Generate the specialized kernel source.
- * kinds[c]: SN_K_* per used column slot (uniform across batches).
- * Layout contract identical to the interpreted kernels:
- *   keyless: scratch row [2*na_t+1] = [sums][counts][rowcount]
- *   grouped: scratch row [nslots*(naggs+1)], rowcount at +naggs.         */
-static std::string gen_source(const sn_dev_plan *p, const int *kinds,
-                              int nslots, int na_t, int has_del) {
-  const int NC = p->nused;
-  const int NA = p->naggs;
+/* ---- plan shape ---------------------------------------------------------
+ * Everything the emitters branch on, decided once. */
+
+#define JIT_CHUNK 1024          /* rows per LDS image chunk */
+#define JIT_WG 256
+#define JIT_MAX_AGGS 12         /* sn_dev_plan.aggs */
+#define JIT_REG_MAX_SLOTS 8     /* most slots the per-lane registers carry */
+#define JIT_REG_MAX_AGGS 6      /* ... and most aggregates per slot */
+#define JIT_LDS_MAX_SLOTS 1024  /* most slots of the block LDS accumulator */
+#define JIT_LDS_BUDGET (160 * 1024)   /* static LDS of one workgroup */
+#define JIT_SLUT_MAX_BYTES (100 * 1024)
+
+/* where a surviving row's aggregate values go — exactly one per kernel */
+enum JitAcc {
+  ACC_KEYLESS,   /* per-lane registers, no slots: [sums][counts][rowcount] */
+  ACC_REGS,      /* per-lane registers per slot, slot-predicated fma */
+  ACC_WBIN,      /* 16 LDS bins of 16 lanes each */
+  ACC_LDS,       /* one block-level LDS accumulator */
+  ACC_GLOBAL,    /* HBM accumulator, privatised 8 ways by XCD */
+  ACC_SPARSE,    /* open-address hash table in HBM, probed per row */
+  ACC_RADIX      /* pass 1 of the radix two-pass: scatter records */
+};
+
+/* how a fact row finds its broadcast-dimension payload */
+enum JitProbe {
+  PROBE_NONE,
+  PROBE_HASH,    /* open-address chain in global memory */
+  PROBE_SPAY,    /* dense int32 LUT, probed from the staged registers */
+  PROBE_SLUT     /* dense LUT packed into 4-bit LDS nibbles */
+};
+
+/* how a row's accumulator slot is computed */
+enum JitSlot {
+  SLOT_NONE,          /* keyless */
+  SLOT_SINGLE,        /* keyless plan in the grouped (pac) layout */
+  SLOT_DENSE,         /* (v0 - base0) * mul0 + (v1 - base1) */
+  SLOT_JOIN_ATTR,     /* the join payload (times jslot_mul + fact slot) */
+  SLOT_SPARSE_PROBE,  /* position in the hash table */
+  SLOT_RADIX_RANK     /* (partition, rank) in the chunk's histogram */
+};
+
+struct JitShape {
+  int NC, NA;        /* used columns, aggregates */
+  int NS, NA1;       /* slots (>= 1), cells per slot row */
+  int nv;            /* doubles per block scratch row */
+  int mm_any;        /* some aggregate is MIN/MAX */
+  JitAcc acc;
+  JitProbe probe;
+  JitSlot slot;
+  long long slut_span, slut_words;
+  int occupancy;     /* second __launch_bounds__ argument */
+};
+
+/* pac: per-agg-count accumulator rows ([sums][counts][rowcount]).  In
+ * the JIT this occurs only for MIN/MAX plans (null-carrying batches are
+ * never JIT-eligible, so counts == rowcount and the count cells simply
+ * mirror the rowcount); mm plans route through the grouped layouts,
+ * keyless included (one slot). */
+static JitAcc jit_acc_mode(int nslots, int naggs, int pac, int sparse,
+                           int radix, int mm_any) {
   /* sparse: open-address hash aggregate — accumulator IS `out` (hacc),
    * key table and flag words arrive via the jkeys/jpayload params, and the
    * capacity is tokenized (read from the device plan) so grow-and-retry
    * reuses one compiled kernel */
-  const int sparse_mode = p->sparse != 0;
   /* radix two-pass: instead of probing the global table per row (64 B
    * random lines across tens of MB — the measured 182 B/row), pass 1
    * scatters (key, agg values) records into 1 << (hcap_log2-12) hash
    * partitions via an LDS-histogram multi-split; k_radix_agg then
    * aggregates each partition into its private L2-resident table segment */
-  const int radix_mode = sparse_mode && p->radix != 0;
-  /* pac: per-agg-count accumulator rows ([sums][counts][rowcount]).  In
-   * the JIT this occurs only for MIN/MAX plans (null-carrying batches are
-   * never JIT-eligible, so counts == rowcount and the count cells simply
-   * mirror the rowcount); mm plans route through the grouped layouts,
-   * keyless included (one slot). */
-  const int pac_mode = p->pac != 0;
-  int mm_any = 0;
-  for (int a = 0; a < NA; a++) mm_any |= p->aggs[a].op != 0;
-  const int NS = nslots < 1 ? 1 : nslots;
-  const int NA1 = pac_mode ? 2 * NA + 1 : NA + 1;
-  const int grouped = nslots > 1 || sparse_mode || pac_mode;
+  if (sparse) return radix ? ACC_RADIX : ACC_SPARSE;
+  if (nslots <= 1 && !pac) return ACC_KEYLESS;
+  if (nslots > JIT_LDS_MAX_SLOTS) return ACC_GLOBAL;
+  /* >8 slots: block-level LDS accumulators (f64 LDS atomics) instead of
+   * per-lane registers — the high-cardinality SHAMap analogue.  Occupancy 1
+   * (the LDS image + accumulator array leave no room for a second group). */
+  if (nslots > JIT_REG_MAX_SLOTS) return ACC_LDS;
+  /* wbin mode: few aggregates over many slots makes the per-slot
+   * select-accumulate VALU-bound (star join: 8 slots x 2 updates vs 2 LDS
+   * atomics per row) — per-wave LDS bins shift the work to the LDS pipe,
+   * which the row phase barely uses.
+   * wbin eligibility: NA<=2 only.  Widening to Q1's 6-slot/5-agg shape was
+   * MEASURED SLOWER (3.51 vs 5.13 TB/s on Q1 SF10): 6 LDS f64 atomics/row
+   * across 16-lane bins conflict harder than the 36 slot-predicated fmas
+   * cost, so the register accumulators stay the measured optimum for
+   * multi-aggregate small-slot shapes. */
+  if (naggs <= 2 && !mm_any && nslots * (naggs + 1) >= 12) return ACC_WBIN;
+  return ACC_REGS;
+}
+
+/* Does the plan's shape fit a query-compiled kernel?  The engine asks before
+ * sn_jit_get; the limits are those of the mode the classifier will pick
+ * (MIN/MAX-ness moves a plan between REGS and WBIN only, which share one). */
+extern "C" int sn_jit_shape_ok(const sn_dev_plan *p) {
+  const int naggs = p->naggs, nslots = p->nslots;
+  const int na1 = p->pac ? 2 * naggs + 1 : naggs + 1;
+  switch (jit_acc_mode(nslots, naggs, p->pac != 0, p->sparse != 0, 0, 0)) {
+    case ACC_KEYLESS: case ACC_SPARSE: case ACC_RADIX:
+      return naggs <= JIT_MAX_AGGS;
+    case ACC_REGS: case ACC_WBIN: return naggs <= JIT_REG_MAX_AGGS;
+    case ACC_LDS:
+      /* LDS-accumulator mode: static shared = LDS image + gacc must fit */
+      return (size_t)p->nused * JIT_CHUNK * 8 + (size_t)nslots * na1 * 8 + 1024
+             <= (size_t)JIT_LDS_BUDGET;
+    case ACC_GLOBAL:
+      /* global-atomic mode: only the LDS image constrains */
+      return nslots <= SN_BIG_GROUP_CAP;
+  }
+  return 0;
+}
+
+static JitShape jit_classify(const sn_dev_plan *p, const int *kinds,
+                             int nslots, int na_t, int has_del) {
+  (void)kinds; (void)has_del;
+  JitShape s;
+  s.NC = p->nused;
+  s.NA = p->naggs;
+  const int sparse = p->sparse != 0, pac = p->pac != 0;
+  s.mm_any = 0;
+  for (int a = 0; a < s.NA; a++) s.mm_any |= p->aggs[a].op != 0;
+  s.NS = nslots < 1 ? 1 : nslots;
+  s.NA1 = pac ? 2 * s.NA + 1 : s.NA + 1;
+  s.acc = jit_acc_mode(nslots, s.NA, pac, sparse, p->radix != 0, s.mm_any);
+  s.nv = s.acc == ACC_KEYLESS ? 2 * na_t + 1 : s.NS * s.NA1;
+
+  /* LDS-packed dense LUT: the star probe's dependent gathers stall on
+   * L2/HBM latency (measured 58% SQ_WAIT_INST issue-stall).  When the
+   * payload fits 4 bits (group-by-attr gid <= 14, or semi-join presence)
+   * and the packed span fits LDS, each workgroup packs the int32 LUT
+   * into nibbles ONCE at kernel start and probes LDS instead.
+   * SN_JIT_SLUT=0 reverts to the register-staged L2 probe. */
+  static const int slut_env = [] {
+    const char *v = getenv("SN_JIT_SLUT");
+    return !v || v[0] != '0';
+  }();
+  s.slut_span = (p->jkeys && p->jlut)
+      ? (long long)(p->jlut_max - p->jlut_min + 1) : 0;
+  s.slut_words = (s.slut_span + 7) / 8;
+  const int slut = slut_env && s.slut_span > 0 &&
+                   (p->jmode == 0 || nslots <= 14) &&
+                   s.slut_words * 4 <= JIT_SLUT_MAX_BYTES;
+  s.probe = !p->jkeys ? PROBE_NONE
+            : slut ? PROBE_SLUT : p->jlut ? PROBE_SPAY : PROBE_HASH;
+
+  if (sparse) s.slot = s.acc == ACC_RADIX ? SLOT_RADIX_RANK : SLOT_SPARSE_PROBE;
+  else if (s.acc == ACC_KEYLESS) s.slot = SLOT_NONE;
+  else if (p->jkeys && p->jmode == 1) s.slot = SLOT_JOIN_ATTR;
+  else s.slot = p->ngroup == 0 ? SLOT_SINGLE : SLOT_DENSE;
+
+  /* sparse is random-probe latency-bound: more waves cover the
+   * dependent loads (its LDS footprint is only the sval image).
+   * SN_JIT_SPOCC overrides for occupancy sweeps. */
+  static const int spocc_env = [] {
+    const char *v = getenv("SN_JIT_SPOCC");
+    return v ? atoi(v) : 0;
+  }();
+  if (sparse) s.occupancy = spocc_env > 0 ? spocc_env : 4;
+  else if (s.acc == ACC_LDS || s.acc == ACC_GLOBAL) s.occupancy = 1;
+  else s.occupancy = s.acc == ACC_WBIN ? 4 : 2;
+  return s;
+}
+
+/* ---- column kinds -------------------------------------------------------
+ * All the generator knows about a stageable column kind.  A chunk of a
+ * column is staged as two registers per lane, two rows each: st<c>_0 holds
+ * rows 2*tid(+1), st<c>_1 rows 2*(tid+WG)(+1); 16-bit kinds pack their two
+ * rows into one unsigned.  The LDS image holds every value as a double,
+ * except that 8-byte kinds keep their raw bits (an i64 converts where it is
+ * read, by the plan's i64_mask). */
+enum JitConv {
+  CV_BITS64,   /* the 8 bytes as they are */
+  CV_NUM,      /* numeric cast */
+  CV_F32,      /* float bits in an int register */
+  CV_DICT      /* dm<c>[index]: premultiplied dictionary contribution */
+};
+struct JitKind {
+  const char *reg;   /* register type of one staged load */
+  int bytes;         /* bytes per row in the column body */
+  const char *mem;   /* row type in the column body */
+  JitConv conv;      /* row -> double of the LDS image */
+  int i64;           /* the 8 bytes are an integer whatever i64_mask says */
+  int store_each;    /* stage_write stores y0 before it forms y1 (the text of
+                        the measured kernels, kept as it is) */
+};
+static const JitKind &jit_kind(int k) {
+  static const JitKind f64 = { "double2_t", 8, "double", CV_BITS64, 0, 0 };
+  static const JitKind i64 = { "double2_t", 8, "double", CV_BITS64, 1, 0 };
+  static const JitKind i32 = { "int2_t", 4, "int", CV_NUM, 0, 1 };
+  static const JitKind f32 = { "int2_t", 4, "float", CV_F32, 0, 0 };
+  static const JitKind d32 = { "int2_t", 4, "int", CV_DICT, 0, 0 };
+  static const JitKind d16 = { "unsigned", 2, "unsigned short", CV_DICT, 0, 0 };
+  static const JitKind i16 = { "unsigned", 2, "short", CV_NUM, 0, 0 };
+  switch (k) {
+    case SN_K_F64: return f64;
+    case SN_K_I64: return i64;
+    case SN_K_I32: return i32;
+    case SN_K_F32: return f32;
+    case SN_K_DICT32: return d32;
+    case SN_K_DICT16: return d16;
+    default: return i16;   /* SN_K_I16; the engine stages no other kind */
+  }
+}
+
+/* staged register row j of column c (j: 0 -> st_0.x row base+2*tid,
+ * 1 -> st_0.y, 2 -> st_1.x row base+2*(tid+WG), 3 -> .y) */
+static std::string kind_reg_row(const JitKind &K, int c, int j) {
+  if (K.bytes == 2)
+    return strf((j & 1) ? "st%d_%d >> 16" : "st%d_%d & 0xffff", c, j >> 1);
+  return strf("st%d_%d.%s", c, j >> 1, (j & 1) ? "y" : "x");
+}
+
+/* the LDS image's double for staged register row j (a CV_F32 row reads the
+ * float2_t view f0/f1 that stage_write declares) */
+static std::string kind_image_from_reg(const JitKind &K, int c, int j) {
+  const std::string r = kind_reg_row(K, c, j);
+  switch (K.conv) {
+    case CV_BITS64: return r;
+    case CV_DICT: return strf("(double)dm%d[%s]", c, r.c_str());
+    case CV_F32: return strf("(double)f%d.%s", j >> 1, (j & 1) ? "y" : "x");
+    default:
+      return K.bytes == 2 ? strf("(double)(short)(%s)", r.c_str())
+                          : strf("(double)%s", r.c_str());
+  }
+}
+
+/* integer key from staged register row j.  Keys are int16/int32/int64
+ * columns (the engine admits no other join key). */
+static std::string kind_key_from_reg(const JitKind &K, int c, int j,
+                                     int is_i64) {
+  const std::string r = kind_reg_row(K, c, j);
+  if (K.bytes == 8)
+    return strf("%s(%s)", is_i64 || K.i64 ? "__double_as_longlong" : "(i64)",
+                r.c_str());
+  return K.bytes == 4 ? strf("(i64)%s", r.c_str())
+                      : strf("(i64)(short)(%s)", r.c_str());
+}
+
+/* the LDS image's double for row base + r, read from global memory */
+static std::string kind_image_from_mem(const JitKind &K, int c) {
+  const std::string m =
+      strf("((const GAS %s *)(body%d))[base + r]", K.mem, c);
+  switch (K.conv) {
+    case CV_BITS64: return m;
+    case CV_DICT:
+      return strf("(double)dm%d[%s%s]", c, K.bytes == 2 ? "(int)" : "",
+                  m.c_str());
+    default: return strf("(double)%s", m.c_str());
+  }
+}
+
+/* ---- emitters -----------------------------------------------------------
+ * Each appends one piece of the kernel to g.o; gen_source gives the order. */
+
+struct Gen {
   std::string o;
+  const sn_dev_plan *p;
+  const int *kinds;
+  int na_t, has_del;
+  JitShape s;
+};
+
+/* trivial factors (a=0, m=1 — plain column reads, the common case) fold
+ * back to the raw product; their triviality is part of the shape hash */
+static bool ftriv(double a, double m) { return a == 0.0 && m == 1.0; }
+
+static bool plan_col_is_i64(const sn_dev_plan *p, int cslot) {
+  return (p->i64_mask >> cslot) & 1u;
+}
+
+/* typedefs, the device-struct layout mirror and the wave helpers; ends with
+ * static_asserts that pin the mirror to the host's own layout, so a field
+ * added to engine_internal.h fails the compile instead of shifting every
+ * tokenized literal the kernel reads */
+static void emit_prelude(std::string &o) {
   o += R"(
 typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef int int2_t __attribute__((ext_vector_type(2)));
@@ -159,35 +413,33 @@ __device__ __forceinline__ u64 mix64(u64 x) {
 }
 )";
   emitf(o, "#define CHUNK %d\n#define WG %d\n#define TILE %d\n",
-        1024, 256, SN_TILE_ROWS);
-  /* >8 slots: block-level LDS accumulators (f64 LDS atomics) instead of
-   * per-lane registers — the high-cardinality SHAMap analogue.  Occupancy 1
-   * (the LDS image + accumulator array leave no room for a second group). */
-  const int glob_mode = (grouped && nslots > 1024) || sparse_mode;
-  const int lds_mode = grouped && nslots > 8 && !glob_mode;
-  /* wbin eligibility: NA<=2 only.  Widening to Q1's 6-slot/5-agg shape was
-   * MEASURED SLOWER (3.51 vs 5.13 TB/s on Q1 SF10): 6 LDS f64 atomics/row
-   * across 16-lane bins conflict harder than the 36 slot-predicated fmas
-   * cost, so the register accumulators stay the measured optimum for
-   * multi-aggregate small-slot shapes. */
-  const int wbin_pre = grouped && !lds_mode && !glob_mode && NA <= 2 &&
-                       !mm_any && nslots * (NA + 1) >= 12;
-  /* predicate folding: evaluate every predicate AT STAGE TIME from the
-   * just-loaded registers and ballot the verdicts into a 16-word LDS
-   * bitmap; the row pass then reads ONE broadcast bit per row instead of
-   * re-reading each predicate column from LDS and comparing.  BUILT AND
-   * MEASURED SLOWER (same-box A/B, 2 rounds each): Q6 SF100 74.9 vs
-   * 75.8%, Q1 SF100 71.9 vs 73.6% — the saved LDS reads/compares were
-   * already hidden under HBM latency, while the stage-time ballots add
-   * v_cmp+SGPR traffic on the critical staging path.  Kept behind
-   * SN_JIT_FOLD=1; default off. */
-  static const int fold_env = [] {
-    const char *v = getenv("SN_JIT_FOLD");
-    return v && v[0] == '1';
-  }();
-  const int fold_preds = fold_env && !sparse_mode &&
-                         (p->npreds_d + p->npreds_i) > 0;
-  emitf(o, "extern \"C\" __global__ __launch_bounds__(WG, %d)\n"
+        JIT_CHUNK, JIT_WG, SN_TILE_ROWS);
+  /* every mirrored size, and the offset of every member the kernel reads */
+#define SZ(T) { "sizeof(" #T ")", sizeof(T) }
+#define OFF(T, M) { "__builtin_offsetof(" #T ", " #M ")", offsetof(T, M) }
+  static const struct { const char *what; size_t is; } pins[] = {
+    SZ(sn_dev_col), SZ(sn_dev_batch), SZ(sn_dev_tile), SZ(sn_dev_pred_d),
+    SZ(sn_dev_pred_i), SZ(sn_dev_agg), SZ(sn_dev_plan),
+    OFF(sn_dev_col, body), OFF(sn_dev_col, dictmap),
+    OFF(sn_dev_batch, num_rows), OFF(sn_dev_batch, del_bm),
+    OFF(sn_dev_batch, cols), OFF(sn_dev_tile, row_start),
+    OFF(sn_dev_pred_d, hi), OFF(sn_dev_pred_i, hi), OFF(sn_dev_agg, m2),
+    OFF(sn_dev_plan, preds_d), OFF(sn_dev_plan, preds_i),
+    OFF(sn_dev_plan, aggs), OFF(sn_dev_plan, inp[1].bm),
+    OFF(sn_dev_plan, inp[1].base), OFF(sn_dev_plan, inp[1].nwords),
+    OFF(sn_dev_plan, hcap_log2), OFF(sn_dev_plan, precs),
+    OFF(sn_dev_plan, pcount), OFF(sn_dev_plan, percap),
+    OFF(sn_dev_plan, radix),
+  };
+#undef SZ
+#undef OFF
+  for (const auto &pin : pins)
+    emitf(o, "static_assert(%s == %zu, \"layout mirror differs from "
+             "engine_internal.h\");\n", pin.what, pin.is);
+}
+
+static void emit_signature(Gen &g) {
+  emitf(g.o, "extern \"C\" __global__ __launch_bounds__(WG, %d)\n"
            "void jit_scan(const sn_dev_batch *__restrict__ batches,\n"
            "              const sn_dev_tile *__restrict__ tiles, int ntiles,\n"
            "              double *__restrict__ out,\n"
@@ -200,24 +452,19 @@ __device__ __forceinline__ u64 mix64(u64 x) {
            "  const GAS int *jlut = (const GAS int *)(u64)jlut_p;\n"
            "  const GAS sn_dev_plan *P = (const GAS sn_dev_plan *)(u64)plan_p;\n"
            "  (void)jkeys; (void)jpayload; (void)jlut; (void)P;\n",
-        /* sparse is random-probe latency-bound: more waves cover the
-         * dependent loads (its LDS footprint is only the sval image).
-         * SN_JIT_SPOCC overrides for occupancy sweeps. */
-        [&] {
-          static const int so = [] {
-            const char *v = getenv("SN_JIT_SPOCC");
-            return v ? atoi(v) : 0;
-          }();
-          if (sparse_mode) return so > 0 ? so : 4;
-          return (lds_mode || glob_mode) ? 1 : (wbin_pre ? 4 : 2);
-        }());
-  /* tokenized plan values (the reference's ParamLiteral tokenization,
-   * TokenizationTest / SnappySession plan cache): predicate bounds and
-   * aggregate coefficients load once per wave from the cached device plan
-   * (uniform scalar loads hoisted to kernel entry), so one compiled
-   * kernel serves every literal value of the same plan SHAPE.  Structure
-   * (counts, columns, neutral factors, group/join/LUT geometry) stays
-   * compile-time. */
+        g.s.occupancy);
+}
+
+/* tokenized plan values (the reference's ParamLiteral tokenization,
+ * TokenizationTest / SnappySession plan cache): predicate bounds and
+ * aggregate coefficients load once per wave from the cached device plan
+ * (uniform scalar loads hoisted to kernel entry), so one compiled
+ * kernel serves every literal value of the same plan SHAPE.  Structure
+ * (counts, columns, neutral factors, group/join/LUT geometry) stays
+ * compile-time. */
+static void emit_literals(Gen &g) {
+  std::string &o = g.o;
+  const sn_dev_plan *p = g.p;
   for (int i = 0; i < p->npreds_d; i++)
     emitf(o, "  const double pd%d_lo = P->preds_d[%d].lo, pd%d_hi = P->preds_d[%d].hi;\n",
           i, i, i, i);
@@ -229,10 +476,7 @@ __device__ __forceinline__ u64 mix64(u64 x) {
              "  const i64 inb%d_base = P->inp[%d].base;\n"
              "  const i64 inb%d_lim = (i64)P->inp[%d].nwords * 64;\n",
           i, i, i, i, i, i);
-  /* trivial factors (a=0, m=1 — plain column reads, the common case) fold
-   * back to the raw product; their triviality is part of the shape hash */
-  auto ftriv = [](double a, double m) { return a == 0.0 && m == 1.0; };
-  for (int a = 0; a < NA; a++) {
+  for (int a = 0; a < g.s.NA; a++) {
     const sn_dev_agg &A = p->aggs[a];
     if (A.nf >= 1 && !ftriv(A.a0, A.m0))
       emitf(o, "  const double ag%d_a0 = P->aggs[%d].a0, ag%d_m0 = P->aggs[%d].m0;\n", a, a, a, a);
@@ -241,434 +485,141 @@ __device__ __forceinline__ u64 mix64(u64 x) {
     if (A.nf >= 3 && !ftriv(A.a2, A.m2))
       emitf(o, "  const double ag%d_a2 = P->aggs[%d].a2, ag%d_m2 = P->aggs[%d].m2;\n", a, a, a, a);
   }
-  /* wbin mode: few aggregates over many slots makes the per-slot
-   * select-accumulate VALU-bound (star join: 8 slots x 2 updates vs 2 LDS
-   * atomics per row) — per-wave LDS bins shift the work to the LDS pipe,
-   * which the row phase barely uses. */
-  const int wbin_mode = wbin_pre;
-  /* fused register pass (the star-join shape): predicate-free dense-LUT
-   * group-by-attr joins skip the LDS image ENTIRELY — probe, mask and
-   * accumulate run straight from the staged registers with no barriers in
-   * the chunk loop.  BUILT AND MEASURED SLOWER than the staged-LDS scheme
-   * on star-join SF10 (2.39 TB/s staged-LDS vs 1.84 single-buffered /
-   * 1.72 value-pipelined / 1.76 probe-pipelined fused): without the LDS
-   * stage the per-chunk dependency chain load->probe->atomic exposes
-   * whichever leg is not double-buffered, and the block-wide barrier the
-   * fusion removes was evidently not the bottleneck.  Kept behind
-   * SN_JIT_FUSE=1 for re-evaluation; default off. */
-  static const int fuse_env = [] {
-    const char *v = getenv("SN_JIT_FUSE");
-    return v && v[0] == '1';
-  }();
-  const int fuse_mode = fuse_env && wbin_mode && p->jkeys && p->jlut &&
-                        p->jmode == 1 && p->jslot_mul == 0 &&
-                        p->npreds_d + p->npreds_i == 0;
-  /* LDS-packed dense LUT: the star probe's dependent gathers stall on
-   * L2/HBM latency (measured 58% SQ_WAIT_INST issue-stall).  When the
-   * payload fits 4 bits (group-by-attr gid <= 14, or semi-join presence)
-   * and the packed span fits LDS, each workgroup packs the int32 LUT
-   * into nibbles ONCE at kernel start and probes LDS instead.
-   * SN_JIT_SLUT=0 reverts to the register-staged L2 probe. */
-  static const int slut_env = [] {
-    const char *v = getenv("SN_JIT_SLUT");
-    return !v || v[0] != '0';
-  }();
-  const long long slut_span = (p->jkeys && p->jlut)
-      ? (long long)(p->jlut_max - p->jlut_min + 1) : 0;
-  const long long slut_words = (slut_span + 7) / 8;
-  const int slut_mode = slut_env && !fuse_mode && slut_span > 0 &&
-                        (p->jmode == 0 || nslots <= 14) &&
-                        slut_words * 4 <= 100 * 1024;
-  if (!fuse_mode) {
-    emitf(o, "  __shared__ __attribute__((aligned(16))) double sval[%d][CHUNK];\n", NC);
-    if (fold_preds)
-      o += "  __shared__ unsigned long long sbits[16];\n";
-  }
-  if (radix_mode)
-    o += "  __shared__ int phist[4096];\n";   /* npart <= 4096 (cap 2^24) */
-  if (!lds_mode && !wbin_mode && !glob_mode)
-    emitf(o, "  __shared__ __attribute__((aligned(16))) double bacc[%d];\n",
-          grouped ? NS * NA1 : 2 * na_t + 1);
-  o += "  const int tid = threadIdx.x;\n";
+}
 
-  /* accumulators */
-  if (sparse_mode) {
-    /* single HBM accumulator (sparse keys -> low per-address contention;
-     * probe position indexes the rows); capacity tokenized from the plan */
-    emitf(o, "  GAS double *gacc = (GAS double *)(u64)out;\n"
-             "  GAS i64 *hkeys = (GAS i64 *)(u64)jkeys_p;\n"
-             "  GAS int *hflags = (GAS int *)(u64)jpayload_p;\n"
-             "  const int hcl = P->hcap_log2;\n"
-             "  const unsigned hmask = (1u << hcl) - 1;\n"
-             "  const int hcap = 1 << hcl;\n"
-             "  (void)gacc; (void)hkeys; (void)hmask; (void)hcap;\n");
-    if (radix_mode)
-      o += "  GAS double *precs = (GAS double *)(u64)P->precs;\n"
+/* zero an LDS accumulator of n cells; with MIN/MAX aggregates (mm) their
+ * cells take the ord-encoding identities instead */
+static void emit_acc_init(std::string &o, const Gen &g, const char *acc,
+                          int n, int mm) {
+  if (!mm) {
+    emitf(o, "  for (int i = tid; i < %d; i += WG) %s[i] = 0.0;\n", n, acc);
+  } else {
+    emitf(o, "  for (int i = tid; i < %d; i += WG) {\n"
+             "    const int a = i %% %d;\n"
+             "    double iv = 0.0;\n", n, g.s.NA1);
+    for (int a = 0; a < g.s.NA; a++)
+      if (g.p->aggs[a].op != 0)
+        emitf(o, "    if (a == %d) iv = __longlong_as_double(%s);\n", a,
+              g.p->aggs[a].op == 1 ? "0xFFF8000000000000ll"
+                                   : "0x0000000000000000ll");
+    emitf(o, "    %s[i] = iv;\n  }\n", acc);
+  }
+  o += "  __syncthreads();\n";
+}
+
+/* the LDS image, then whatever holds the aggregates during the scan */
+static void emit_acc_decl(Gen &g) {
+  std::string &o = g.o;
+  const JitShape &s = g.s;
+  emitf(o, "  __shared__ __attribute__((aligned(16))) double sval[%d][CHUNK];\n", s.NC);
+  /* shared arrays precede tid in the text; the rest of each mode follows */
+  std::string d;
+  const char *bacc = "  __shared__ __attribute__((aligned(16))) double bacc[%d];\n";
+  const char *sparse_tables =
+      /* single HBM accumulator (sparse keys -> low per-address contention;
+       * probe position indexes the rows); capacity tokenized from the plan */
+      "  GAS double *gacc = (GAS double *)(u64)out;\n"
+      "  GAS i64 *hkeys = (GAS i64 *)(u64)jkeys_p;\n"
+      "  GAS int *hflags = (GAS int *)(u64)jpayload_p;\n"
+      "  const int hcl = P->hcap_log2;\n"
+      "  const unsigned hmask = (1u << hcl) - 1;\n"
+      "  const int hcap = 1 << hcl;\n"
+      "  (void)gacc; (void)hkeys; (void)hmask; (void)hcap;\n";
+  switch (s.acc) {
+    case ACC_RADIX:
+      o += "  __shared__ int phist[4096];\n";   /* npart <= 4096 (cap 2^24) */
+      d += sparse_tables;
+      d += "  GAS double *precs = (GAS double *)(u64)P->precs;\n"
            "  GAS int *pcount = (GAS int *)(u64)P->pcount;\n"
            "  const int percap = P->percap;\n"
            "  const int npart = 1 << (hcl - P->radix);\n";
-  } else if (glob_mode) {
-    /* HBM accumulator IS the out/scratch pointer (host-zeroed), privatized
-     * 8 ways by XCD (blockIdx & 7 matches the dispatch round-robin) so
-     * same-slot atomics from different XCDs never contend and stay in the
-     * local L2; k_reduce folds the 8 copies */
-    emitf(o, "  GAS double *gacc = (GAS double *)(u64)out"
-             " + (u64)(blockIdx.x & 7) * %d;\n", NS * NA1);
-  } else if (lds_mode) {
-    /* block-level LDS accumulator, initialized once (min/max cells take
-     * their ord-encoding identities), flushed once at the end */
-    emitf(o, "  __shared__ __attribute__((aligned(16))) double gacc[%d];\n",
-          NS * NA1);
-    if (!mm_any) {
-      emitf(o, "  for (int i = tid; i < %d; i += WG) gacc[i] = 0.0;\n",
-            NS * NA1);
-    } else {
-      emitf(o, "  for (int i = tid; i < %d; i += WG) {\n"
-               "    const int a = i %% %d;\n"
-               "    double iv = 0.0;\n", NS * NA1, NA1);
-      for (int a = 0; a < NA; a++)
-        if (p->aggs[a].op != 0)
-          emitf(o, "    if (a == %d) iv = __longlong_as_double(%s);\n", a,
-                p->aggs[a].op == 1 ? "0xFFF8000000000000ll"
-                                   : "0x0000000000000000ll");
-      o += "    gacc[i] = iv;\n  }\n";
-    }
-    o += "  __syncthreads();\n";
-  } else if (wbin_mode) {
-    /* 16 bins of 16 lanes each: ~2-way LDS atomic conflicts instead of the
-     * 8-way a per-wave bin sees (measured: issue-stall bound, 58% of wave
-     * cycles in SQ_WAIT_INST_ANY with per-wave bins) */
-    emitf(o, "  __shared__ __attribute__((aligned(16))) double wbin[16][%d];\n"
-             "  for (int i = tid; i < 16 * %d; i += WG)\n"
-             "    ((double *)wbin)[i] = 0.0;\n"
-             "  __syncthreads();\n",
-          NS * NA1, NS * NA1);
-  } else if (grouped) {
-    emitf(o, "  double sums[%d][%d]; double rc[%d];\n", NS, NA, NS);
-    emitf(o, "#pragma unroll\n  for (int s = 0; s < %d; s++) {\n"
-             "    rc[s] = 0;\n", NS);
-    for (int a = 0; a < NA; a++) {
-      const int op = p->aggs[a].op;
-      if (op == 0) emitf(o, "    sums[s][%d] = 0.0;\n", a);
-      else emitf(o, "    sums[s][%d] = __longlong_as_double(%s);\n", a,
-                 op == 1 ? "0x7FF0000000000000ll" : "0xFFF0000000000000ll");
-    }
-    o += "  }\n";
-  } else {
-    emitf(o, "  double sums[%d], cnts[%d], rcnt = 0.0;\n", NA, NA);
-    emitf(o, "#pragma unroll\n  for (int a = 0; a < %d; a++) { sums[a] = 0; cnts[a] = 0; }\n", NA);
+      break;
+    case ACC_SPARSE:
+      d += sparse_tables;
+      break;
+    case ACC_GLOBAL:
+      /* HBM accumulator IS the out/scratch pointer (host-zeroed), privatized
+       * 8 ways by XCD (blockIdx & 7 matches the dispatch round-robin) so
+       * same-slot atomics from different XCDs never contend and stay in the
+       * local L2; k_reduce folds the 8 copies */
+      emitf(d, "  GAS double *gacc = (GAS double *)(u64)out"
+               " + (u64)(blockIdx.x & 7) * %d;\n", s.nv);
+      break;
+    case ACC_LDS:
+      /* block-level LDS accumulator, initialized once (min/max cells take
+       * their ord-encoding identities), flushed once at the end */
+      emitf(d, "  __shared__ __attribute__((aligned(16))) double gacc[%d];\n",
+            s.nv);
+      emit_acc_init(d, g, "gacc", s.nv, s.mm_any);
+      break;
+    case ACC_WBIN:
+      /* 16 bins of 16 lanes each: ~2-way LDS atomic conflicts instead of the
+       * 8-way a per-wave bin sees (measured: issue-stall bound, 58% of wave
+       * cycles in SQ_WAIT_INST_ANY with per-wave bins) */
+      emitf(d, "  __shared__ __attribute__((aligned(16))) double wbin[16][%d];\n"
+               "  for (int i = tid; i < 16 * %d; i += WG)\n"
+               "    ((double *)wbin)[i] = 0.0;\n"
+               "  __syncthreads();\n",
+            s.nv, s.nv);
+      break;
+    case ACC_REGS:
+      emitf(o, bacc, s.nv);
+      emitf(d, "  double sums[%d][%d]; double rc[%d];\n", s.NS, s.NA, s.NS);
+      emitf(d, "#pragma unroll\n  for (int s = 0; s < %d; s++) {\n"
+               "    rc[s] = 0;\n", s.NS);
+      for (int a = 0; a < s.NA; a++) {
+        const int op = g.p->aggs[a].op;
+        if (op == 0) emitf(d, "    sums[s][%d] = 0.0;\n", a);
+        else emitf(d, "    sums[s][%d] = __longlong_as_double(%s);\n", a,
+                   op == 1 ? "0x7FF0000000000000ll" : "0xFFF0000000000000ll");
+      }
+      d += "  }\n";
+      break;
+    case ACC_KEYLESS:
+      emitf(o, bacc, s.nv);
+      emitf(d, "  double sums[%d], cnts[%d], rcnt = 0.0;\n", s.NA, s.NA);
+      emitf(d, "#pragma unroll\n  for (int a = 0; a < %d; a++) { sums[a] = 0; cnts[a] = 0; }\n", s.NA);
+      break;
   }
+  o += "  const int tid = threadIdx.x;\n";
+  o += d;
+}
 
-  if (p->jkeys && p->jlut && !fuse_mode && !slut_mode)
-    o += "  __shared__ int spay[CHUNK];\n";
-  if (slut_mode)
-    emitf(o, "  __shared__ unsigned slut[%lld];\n", slut_words);
+static void emit_probe_decl(Gen &g) {
+  if (g.s.probe == PROBE_SPAY)
+    g.o += "  __shared__ int spay[CHUNK];\n";
+  if (g.s.probe == PROBE_SLUT)
+    emitf(g.o, "  __shared__ unsigned slut[%lld];\n", g.s.slut_words);
+}
 
-  /* staged register buffers: per column, by width class (fuse mode adds a
-   * second set, B, so the previous chunk processes under the current
-   * chunk's in-flight loads) */
-  for (int c = 0; c < NC; c++) {
-    int k = kinds[c];
-    const char *ty = (k == SN_K_F64 || k == SN_K_I64) ? "double2_t"
-                     : (k == SN_K_I32 || k == SN_K_F32 || k == SN_K_DICT32)
-                           ? "int2_t" : "unsigned";
-    emitf(o, "  %s st%d_0, st%d_1;\n", ty, c, c);
-    if (fuse_mode) emitf(o, "  %s stB%d_0, stB%d_1;\n", ty, c, c);
-  }
+/* staged register buffers: per column, by width class */
+static void emit_stage_regs(Gen &g) {
+  for (int c = 0; c < g.s.NC; c++)
+    emitf(g.o, "  %s st%d_0, st%d_1;\n", jit_kind(g.kinds[c]).reg, c, c);
+}
 
-  /* stage_load body, emitted in the prologue and inside the chunk loop;
-   * `pre` picks the destination register set ("st" or fuse-mode "stB") */
-  auto emit_load_pre = [&](const char *base_expr, const char *ind,
-                           const char *pre) {
-    for (int c = 0; c < NC; c++) {
-      int k = kinds[c];
-      if (k == SN_K_F64 || k == SN_K_I64) {
-        emitf(o, "%s%s%d_0 = ((const GAS double2_t *)(body%d + (u64)(%s) * 8))[tid];\n", ind, pre, c, c, base_expr);
-        emitf(o, "%s%s%d_1 = ((const GAS double2_t *)(body%d + (u64)(%s) * 8))[tid + WG];\n", ind, pre, c, c, base_expr);
-      } else if (k == SN_K_I32 || k == SN_K_F32 || k == SN_K_DICT32) {
-        emitf(o, "%s%s%d_0 = ((const GAS int2_t *)(body%d + (u64)(%s) * 4))[tid];\n", ind, pre, c, c, base_expr);
-        emitf(o, "%s%s%d_1 = ((const GAS int2_t *)(body%d + (u64)(%s) * 4))[tid + WG];\n", ind, pre, c, c, base_expr);
-      } else {
-        emitf(o, "%s%s%d_0 = ((const GAS unsigned *)(body%d + (u64)(%s) * 2))[tid];\n", ind, pre, c, c, base_expr);
-        emitf(o, "%s%s%d_1 = ((const GAS unsigned *)(body%d + (u64)(%s) * 2))[tid + WG];\n", ind, pre, c, c, base_expr);
-      }
-    }
-  };
-  auto emit_load = [&](const char *base_expr, const char *ind) {
-    emit_load_pre(base_expr, ind, "st");
-  };
+/* pack the dense LUT into 4-bit LDS nibbles, once per workgroup:
+ * 15 = absent; group-by-attr payloads are gids <= 14 (structural
+ * gate), semi-join presence packs as 0 */
+static void emit_slut_pack(Gen &g) {
+  emitf(g.o, "  for (unsigned i = tid; i < %lldu; i += WG) {\n"
+           "    unsigned wd = 0u;\n"
+           "#pragma unroll\n"
+           "    for (int j = 0; j < 8; j++) {\n"
+           "      const long long ix = (long long)i * 8 + j;\n"
+           "      const int v = ix < %lldll ? jlut[ix] : -1;\n"
+           "      const unsigned nib = v < 0 ? 15u : %s;\n"
+           "      wd |= nib << (4 * j);\n"
+           "    }\n"
+           "    slut[i] = wd;\n"
+           "  }\n"
+           "  __syncthreads();\n",
+        g.s.slut_words, g.s.slut_span, g.p->jmode == 0 ? "0u" : "(unsigned)v");
+}
 
-  /* value of column c at staged-register row j (j: 0 -> st_0.x row
-   * base+2*tid, 1 -> st_0.y, 2 -> st_1.x row base+2*(tid+WG), 3 -> .y) */
-  auto rexpr = [&](int c, int j) -> std::string {
-      char buf[96];
-      const int h = j >> 1, lo = !(j & 1);
-      const char *xy = (j & 1) ? "y" : "x";
-      switch (kinds[c]) {
-        case SN_K_F64:
-          snprintf(buf, 96, "st%d_%d.%s", c, h, xy); break;
-        case SN_K_I64:
-          snprintf(buf, 96, "(double)__double_as_longlong(st%d_%d.%s)", c, h, xy); break;
-        case SN_K_I32:
-          snprintf(buf, 96, "(double)st%d_%d.%s", c, h, xy); break;
-        case SN_K_F32:
-          snprintf(buf, 96, "(double)((const float *)&st%d_%d)[%d]", c, h, j & 1); break;
-        case SN_K_DICT32:
-          snprintf(buf, 96, "(double)dm%d[st%d_%d.%s]", c, c, h, xy); break;
-        case SN_K_DICT16:
-          snprintf(buf, 96, lo ? "(double)dm%d[st%d_%d & 0xffff]"
-                               : "(double)dm%d[st%d_%d >> 16]", c, c, h); break;
-        default: /* I16 */
-          snprintf(buf, 96, lo ? "(double)(short)(st%d_%d & 0xffff)"
-                               : "(double)(short)(st%d_%d >> 16)", c, h); break;
-      }
-      return buf;
-    };
-    auto kexpr_reg = [&](int c, int j) -> std::string {
-      char buf[96];
-      const int h = j >> 1, lo = !(j & 1);
-      const char *xy = (j & 1) ? "y" : "x";
-      const int is_i64 = (p->i64_mask >> c) & 1u;
-      switch (kinds[c]) {
-        case SN_K_I32: snprintf(buf, 96, "(i64)st%d_%d.%s", c, h, xy); break;
-        case SN_K_F64: case SN_K_I64:
-          snprintf(buf, 96, "%s(st%d_%d.%s)",
-                   is_i64 || kinds[c] == SN_K_I64 ? "__double_as_longlong" : "(i64)",
-                   c, h, xy);
-          break;
-        default:
-          snprintf(buf, 96, lo ? "(i64)(short)(st%d_%d & 0xffff)"
-                               : "(i64)(short)(st%d_%d >> 16)", c, h); break;
-      }
-      return buf;
-  };
-
-  if (fuse_mode) {
-    auto va_fused = [&](int a, const std::string (&f)[3]) -> std::string {
-      const sn_dev_agg &A = p->aggs[a];
-      if (A.nf < 1) return "1.0";
-      char t0[192], t1[192], t2[192];
-      if (ftriv(A.a0, A.m0)) snprintf(t0, 192, "%s", f[0].c_str());
-      else snprintf(t0, 192, "__builtin_fma(ag%d_m0, %s, ag%d_a0)", a, f[0].c_str(), a);
-      std::string r = t0;
-      if (A.nf >= 2) {
-        if (ftriv(A.a1, A.m1)) snprintf(t1, 192, "%s", f[1].c_str());
-        else snprintf(t1, 192, "__builtin_fma(ag%d_m1, %s, ag%d_a1)", a, f[1].c_str(), a);
-        r += " * "; r += t1;
-      }
-      if (A.nf >= 3) {
-        if (ftriv(A.a2, A.m2)) snprintf(t2, 192, "%s", f[2].c_str());
-        else snprintf(t2, 192, "__builtin_fma(ag%d_m2, %s, ag%d_a2)", a, f[2].c_str(), a);
-        r += " * "; r += t2;
-      }
-      return r;
-    };
-    /* one row's probe + accumulate */
-    auto emit_row = [&](const std::string &key, const char *rowi,
-                        const std::string (&vas)[12]) {
-      emitf(o, "      { const i64 fk = %s;\n"
-               "        const int inr = (fk >= %lldll) & (fk <= %lldll);\n"
-               "        const i64 ck = fk < %lldll ? %lldll : (fk > %lldll ? %lldll : fk);\n"
-               "        int pay = inr ? jlut[ck - %lldll] : -1;\n"
-               "        int okj = pay >= 0;\n",
-            key.c_str(),
-            (long long)p->jlut_min, (long long)p->jlut_max,
-            (long long)p->jlut_min, (long long)p->jlut_min,
-            (long long)p->jlut_max, (long long)p->jlut_max,
-            (long long)p->jlut_min);
-      if (has_del)
-        emitf(o, "        if (del) { const int gr = %s;\n"
-                 "          okj &= (int)(~(del[(u64)gr >> 6] >> (gr & 63)) & 1ull); }\n",
-              rowi);
-      emitf(o, "        if (okj) {\n"
-               "          double *rw = &wbin[tid >> 4][(pay > 0 ? pay : 0) * %d];\n"
-               "          atomicAdd(&rw[%d], 1.0);\n", NA + 1, NA);
-      for (int a = 0; a < NA; a++)
-        emitf(o, "          atomicAdd(&rw[%d], %s);\n", a, vas[a].c_str());
-      o += "        }\n      }\n";
-    };
-
-    o += R"(
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + TILE, num_rows);
-)";
-    if (has_del)
-      o += "    const GAS u64 *del = (const GAS u64 *)(u64)b.del_bm;\n";
-    for (int c = 0; c < NC; c++) {
-      emitf(o, "    const GAS char *body%d = (const GAS char *)(unsigned long long)b.cols[%d].body;\n", c, c);
-      if (kinds[c] == SN_K_DICT16 || kinds[c] == SN_K_DICT32)
-        emitf(o, "    const GAS int *dm%d = (const GAS int *)(unsigned long long)b.cols[%d].dictmap;\n", c, c);
-    }
-    /* probe block: LUT gathers issued from the B set's key registers RIGHT
-     * AFTER the loads, so they fly a full pipeline stage before the
-     * accumulate consumes them (the round-1 measured optimum, minus LDS) */
-    std::string probe;
-    {
-      std::string keep = std::move(o);
-      o.clear();
-      for (int j = 0; j < 4; j++) {
-        /* kexpr against the B set: build from kexpr_reg then prefix-swap is
-         * fragile; emit directly with the helper on a temp name */
-        std::string kx = kexpr_reg(p->jcslot, j);
-        /* retarget st{c}_ -> stB{c}_ (the key expr references exactly one
-         * register name, emitted by kexpr_reg as "st<digit>") */
-        size_t ppos = 0;
-        while ((ppos = kx.find("st", ppos)) != std::string::npos) {
-          if (ppos + 2 < kx.size() && kx[ppos + 2] >= '0' && kx[ppos + 2] <= '9')
-            kx.insert(ppos + 2, "B");
-          ppos += 3;
-        }
-        char pd[32];
-        snprintf(pd, 32, "payB%d", j);
-        emitf(o, "        { const i64 fk = %s;\n"
-                 "          const int inr = (fk >= %lldll) & (fk <= %lldll);\n"
-                 "          const i64 ck = fk < %lldll ? %lldll : (fk > %lldll ? %lldll : fk);\n"
-                 "          %s = inr ? jlut[ck - %lldll] : -1; }\n",
-              kx.c_str(),
-              (long long)p->jlut_min, (long long)p->jlut_max,
-              (long long)p->jlut_min, (long long)p->jlut_min,
-              (long long)p->jlut_max, (long long)p->jlut_max,
-              pd, (long long)p->jlut_min);
-      }
-      probe = std::move(o);
-      o = std::move(keep);
-    }
-    /* accumulate block: consumes the A set + carried payA payloads */
-    std::string proc;
-    {
-      std::string keep = std::move(o);
-      o.clear();
-      for (int j = 0; j < 4; j++) {
-        char rowi[48];
-        if (j < 2) snprintf(rowi, 48, "pbase + 2 * tid + %d", j);
-        else snprintf(rowi, 48, "pbase + 2 * (tid + WG) + %d", j & 1);
-        std::string vas[12];
-        for (int a = 0; a < NA; a++) {
-          const sn_dev_agg &A = p->aggs[a];
-          std::string f3[3];
-          f3[0] = A.nf >= 1 ? rexpr(A.c0, j) : "1.0";
-          f3[1] = A.nf >= 2 ? rexpr(A.c1, j) : "1.0";
-          f3[2] = A.nf >= 3 ? rexpr(A.c2, j) : "1.0";
-          vas[a] = va_fused(a, f3);
-        }
-        emitf(o, "      { const int pay = payA%d;\n"
-                 "        int okj = pay >= 0;\n", j);
-        if (has_del)
-          emitf(o, "        if (del) { const int gr = %s;\n"
-                   "          okj &= (int)(~(del[(u64)gr >> 6] >> (gr & 63)) & 1ull); }\n",
-                rowi);
-        emitf(o, "        if (okj) {\n"
-                 "          double *rw = &wbin[tid >> 4][(pay > 0 ? pay : 0) * %d];\n"
-                 "          atomicAdd(&rw[%d], 1.0);\n", NA + 1, NA);
-        for (int a = 0; a < NA; a++)
-          emitf(o, "          atomicAdd(&rw[%d], %s);\n", a, vas[a].c_str());
-        o += "        }\n      }\n";
-      }
-      proc = std::move(o);
-      o = std::move(keep);
-    }
-    std::string bcopy;
-    for (int c = 0; c < NC; c++) {
-      char cb[96];
-      snprintf(cb, 96, "        st%d_0 = stB%d_0; st%d_1 = stB%d_1;\n",
-               c, c, c, c);
-      bcopy += cb;
-    }
-    bcopy += "        payA0 = payB0; payA1 = payB1;"
-             " payA2 = payB2; payA3 = payB3;\n";
-    o += "  int payA0 = -1, payA1 = -1, payA2 = -1, payA3 = -1;\n"
-         "  int payB0, payB1, payB2, payB3;\n";
-    o += "    int pbase = -1;\n"
-         "    for (int base = tile.row_start; base < tile_end; base += CHUNK) {\n"
-         "      const int rows = min(CHUNK, tile_end - base);\n"
-         "      if (rows == CHUNK) {\n";
-    /* issue this chunk's loads into B, accumulate the PREVIOUS chunk from
-     * A (probes already in flight since last iteration), then probe B's
-     * keys (gathers fly through the next load+accumulate) and rotate */
-    emit_load_pre("base", "        ", "stB");
-    o += "        if (pbase >= 0) {\n" + proc + "        }\n" + probe + bcopy +
-         "        pbase = base;\n";
-    /* scalar tail: drain the pipeline, then direct global reads */
-    o += "      } else {\n"
-         "        if (pbase >= 0) {\n" + proc + "          pbase = -1;\n"
-         "        }\n"
-         "        for (int r = tid; r < rows; r += WG) {\n"
-         "          const int gr = base + r;\n";
-    auto sexpr = [&](int c) -> std::string {
-      char buf[96];
-      switch (kinds[c]) {
-        case SN_K_F64: snprintf(buf, 96, "((const GAS double *)body%d)[gr]", c); break;
-        case SN_K_I64: snprintf(buf, 96, "(double)((const GAS i64 *)body%d)[gr]", c); break;
-        case SN_K_I32: snprintf(buf, 96, "(double)((const GAS int *)body%d)[gr]", c); break;
-        case SN_K_F32: snprintf(buf, 96, "(double)((const GAS float *)body%d)[gr]", c); break;
-        case SN_K_DICT32: snprintf(buf, 96, "(double)dm%d[((const GAS int *)body%d)[gr]]", c, c); break;
-        case SN_K_DICT16: snprintf(buf, 96, "(double)dm%d[(int)((const GAS unsigned short *)body%d)[gr]]", c, c); break;
-        default: snprintf(buf, 96, "(double)((const GAS short *)body%d)[gr]", c); break;
-      }
-      return buf;
-    };
-    {
-      char kb[96];
-      const int jc = p->jcslot;
-      const int is_i64 = (p->i64_mask >> jc) & 1u;
-      switch (kinds[jc]) {
-        case SN_K_I32: snprintf(kb, 96, "(i64)((const GAS int *)body%d)[gr]", jc); break;
-        case SN_K_F64: case SN_K_I64:
-          snprintf(kb, 96, "%s((const GAS double *)body%d)[gr]%s",
-                   is_i64 || kinds[jc] == SN_K_I64 ? "__double_as_longlong(" : "(i64)(",
-                   jc, ")");
-          break;
-        default: snprintf(kb, 96, "(i64)((const GAS short *)body%d)[gr]", jc); break;
-      }
-      std::string vas[12];
-      for (int a = 0; a < NA; a++) {
-        const sn_dev_agg &A = p->aggs[a];
-        std::string f3[3];
-        f3[0] = A.nf >= 1 ? sexpr(A.c0) : "1.0";
-        f3[1] = A.nf >= 2 ? sexpr(A.c1) : "1.0";
-        f3[2] = A.nf >= 3 ? sexpr(A.c2) : "1.0";
-        vas[a] = va_fused(a, f3);
-      }
-      emit_row(kb, "gr", vas);
-    }
-    o += "        }\n"
-         "      }\n"
-         "    }\n"
-         "    if (pbase >= 0) {\n" + proc + "    }\n"
-         "  }\n";
-    int nvf = nslots * (NA + 1);
-    emitf(o, "  __syncthreads();\n"
-             "  for (int i = tid; i < %d; i += WG) {\n"
-             "    double acc = 0.0;\n"
-             "#pragma unroll\n"
-             "    for (int w = 0; w < 16; w++) acc += wbin[w][i];\n"
-             "    out[(u64)blockIdx.x * %d + i] = acc;\n"
-             "  }\n"
-             "}\n", nvf, nvf);
-    return o;
-  }
-
-  if (slut_mode) {
-    /* pack the dense LUT into 4-bit LDS nibbles, once per workgroup:
-     * 15 = absent; group-by-attr payloads are gids <= 14 (structural
-     * gate), semi-join presence packs as 0 */
-    emitf(o, "  for (unsigned i = tid; i < %lldu; i += WG) {\n"
-             "    unsigned wd = 0u;\n"
-             "#pragma unroll\n"
-             "    for (int j = 0; j < 8; j++) {\n"
-             "      const long long ix = (long long)i * 8 + j;\n"
-             "      const int v = ix < %lldll ? jlut[ix] : -1;\n"
-             "      const unsigned nib = v < 0 ? 15u : %s;\n"
-             "      wd |= nib << (4 * j);\n"
-             "    }\n"
-             "    slut[i] = wd;\n"
-             "  }\n"
-             "  __syncthreads();\n",
-          slut_words, slut_span, p->jmode == 0 ? "0u" : "(unsigned)v");
-  }
+/* tile loop head; hoist body/dict pointers */
+static void emit_tile_prologue(Gen &g) {
+  std::string &o = g.o;
   o += R"(
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const sn_dev_tile tile = tiles[t];
@@ -676,247 +627,154 @@ __device__ __forceinline__ u64 mix64(u64 x) {
     const int num_rows = b.num_rows;
     const int tile_end = min(tile.row_start + TILE, num_rows);
 )";
-  /* hoist body/dict pointers */
-  if (has_del)
+  if (g.has_del)
     o += "    const GAS u64 *del = (const GAS u64 *)(u64)b.del_bm;\n";
-  for (int c = 0; c < NC; c++) {
+  for (int c = 0; c < g.s.NC; c++) {
     emitf(o, "    const GAS char *body%d = (const GAS char *)(unsigned long long)b.cols[%d].body;\n", c, c);
-    if (kinds[c] == SN_K_DICT16 || kinds[c] == SN_K_DICT32)
+    if (jit_kind(g.kinds[c]).conv == CV_DICT)
       emitf(o, "    const GAS int *dm%d = (const GAS int *)(unsigned long long)b.cols[%d].dictmap;\n", c, c);
   }
+}
 
-  auto emit_write = [&](const char *ind) {
-    for (int c = 0; c < NC; c++) {
-      int k = kinds[c];
-      if (k == SN_K_F64 || k == SN_K_I64) {
-        emitf(o, "%s((double2_t *)sval[%d])[tid] = st%d_0;\n", ind, c, c);
-        emitf(o, "%s((double2_t *)sval[%d])[tid + WG] = st%d_1;\n", ind, c, c);
-      } else if (k == SN_K_I32) {
-        emitf(o, "%s{ double2_t y0; y0.x = (double)st%d_0.x; y0.y = (double)st%d_0.y;\n"
-                 "%s  ((double2_t *)sval[%d])[tid] = y0;\n"
-                 "%s  double2_t y1; y1.x = (double)st%d_1.x; y1.y = (double)st%d_1.y;\n"
-                 "%s  ((double2_t *)sval[%d])[tid + WG] = y1; }\n",
-              ind, c, c, ind, c, ind, c, c, ind, c);
-      } else if (k == SN_K_F32) {
-        emitf(o, "%s{ float2_t f0 = *(float2_t *)&st%d_0, f1 = *(float2_t *)&st%d_1;\n"
-                 "%s  double2_t y0; y0.x = (double)f0.x; y0.y = (double)f0.y;\n"
-                 "%s  double2_t y1; y1.x = (double)f1.x; y1.y = (double)f1.y;\n"
-                 "%s  ((double2_t *)sval[%d])[tid] = y0;\n"
-                 "%s  ((double2_t *)sval[%d])[tid + WG] = y1; }\n",
-              ind, c, c, ind, ind, ind, c, ind, c);
-      } else if (k == SN_K_DICT32) {
-        emitf(o, "%s{ double2_t y0; y0.x = (double)dm%d[st%d_0.x]; y0.y = (double)dm%d[st%d_0.y];\n"
-                 "%s  double2_t y1; y1.x = (double)dm%d[st%d_1.x]; y1.y = (double)dm%d[st%d_1.y];\n"
-                 "%s  ((double2_t *)sval[%d])[tid] = y0;\n"
-                 "%s  ((double2_t *)sval[%d])[tid + WG] = y1; }\n",
-              ind, c, c, c, c, ind, c, c, c, c, ind, c, ind, c);
-      } else if (k == SN_K_DICT16) {
-        emitf(o, "%s{ double2_t y0; y0.x = (double)dm%d[st%d_0 & 0xffff]; y0.y = (double)dm%d[st%d_0 >> 16];\n"
-                 "%s  double2_t y1; y1.x = (double)dm%d[st%d_1 & 0xffff]; y1.y = (double)dm%d[st%d_1 >> 16];\n"
-                 "%s  ((double2_t *)sval[%d])[tid] = y0;\n"
-                 "%s  ((double2_t *)sval[%d])[tid + WG] = y1; }\n",
-              ind, c, c, c, c, ind, c, c, c, c, ind, c, ind, c);
-      } else { /* I16 signed */
-        emitf(o, "%s{ double2_t y0; y0.x = (double)(short)(st%d_0 & 0xffff); y0.y = (double)(short)(st%d_0 >> 16);\n"
-                 "%s  double2_t y1; y1.x = (double)(short)(st%d_1 & 0xffff); y1.y = (double)(short)(st%d_1 >> 16);\n"
-                 "%s  ((double2_t *)sval[%d])[tid] = y0;\n"
-                 "%s  ((double2_t *)sval[%d])[tid + WG] = y1; }\n",
-              ind, c, c, ind, c, c, ind, c, ind, c);
-      }
-    }
-  };
+/* stage_load body, emitted in the prologue and inside the chunk loop */
+static void emit_stage_load(Gen &g, const char *base_expr, const char *ind) {
+  for (int c = 0; c < g.s.NC; c++) {
+    const JitKind &K = jit_kind(g.kinds[c]);
+    emitf(g.o, "%sst%d_0 = ((const GAS %s *)(body%d + (u64)(%s) * %d))[tid];\n",
+          ind, c, K.reg, c, base_expr, K.bytes);
+    emitf(g.o, "%sst%d_1 = ((const GAS %s *)(body%d + (u64)(%s) * %d))[tid + WG];\n",
+          ind, c, K.reg, c, base_expr, K.bytes);
+  }
+}
 
-  /* LUT probe straight from the staged key registers, BEFORE they are
-   * written to LDS: the dependent LUT gathers then overlap the stage_write
-   * + barrier + next stage_load instead of stalling the row pass
-   * (measured: in-pass probing leaves 35% of wave cycles parked).
-   * Register mapping: st_0 covers rows 2*tid(+1), st_1 rows 2*(tid+WG)(+1);
-   * the row pass reads spay[tid + k*WG] after the barrier. */
-  auto emit_lut_probe = [&](const std::string &kexpr, const std::string &dst,
-                            const char *ind) {
-    emitf(o, "%s{ const i64 key = %s;\n"
-             "%s  const int inr = (key >= %lldll) & (key <= %lldll);\n"
-             "%s  const i64 ck = key < %lldll ? %lldll : (key > %lldll ? %lldll : key);\n"
-             "%s  const int pv = jlut[ck - %lldll];\n"
-             "%s  %s = inr ? pv : -1; }\n",
-          ind, kexpr.c_str(),
-          ind, (long long)p->jlut_min, (long long)p->jlut_max,
-          ind, (long long)p->jlut_min, (long long)p->jlut_min,
-          (long long)p->jlut_max, (long long)p->jlut_max,
-          ind, (long long)p->jlut_min,
-          ind, dst.c_str());
-  };
-  const int use_spay = p->jkeys && p->jlut && !slut_mode;
-  o += "    int staged = 0;\n"
-       "    if (tile.row_start + CHUNK <= tile_end) {\n";
-  emit_load("tile.row_start", "      ");
-  o += "      staged = 1;\n    }\n"
-       "    for (int base = tile.row_start; base < tile_end; base += CHUNK) {\n"
-       "      const int rows = min(CHUNK, tile_end - base);\n";
-  if (radix_mode)   /* previous chunk's scatter is behind the tail barrier */
-    o += "      for (int i = tid; i < npart; i += WG) phist[i] = 0;\n";
-  o += "      if (staged) {\n";
-  if (use_spay) {
-    const int jc = p->jcslot;
-    const int jk = kinds[jc];
-    int is_i64 = (p->i64_mask >> jc) & 1u;
-    char b0[64], b1[64], b2[64], b3[64];
-    if (jk == SN_K_I32) {
-      snprintf(b0, 64, "(i64)st%d_0.x", jc); snprintf(b1, 64, "(i64)st%d_0.y", jc);
-      snprintf(b2, 64, "(i64)st%d_1.x", jc); snprintf(b3, 64, "(i64)st%d_1.y", jc);
-    } else if (jk == SN_K_F64 || jk == SN_K_I64) {
-      const char *cv = is_i64 || jk == SN_K_I64 ? "__double_as_longlong" : "(i64)";
-      snprintf(b0, 64, "%s(st%d_0.x)", cv, jc); snprintf(b1, 64, "%s(st%d_0.y)", cv, jc);
-      snprintf(b2, 64, "%s(st%d_1.x)", cv, jc); snprintf(b3, 64, "%s(st%d_1.y)", cv, jc);
-    } else { /* I16 */
-      snprintf(b0, 64, "(i64)(short)(st%d_0 & 0xffff)", jc);
-      snprintf(b1, 64, "(i64)(short)(st%d_0 >> 16)", jc);
-      snprintf(b2, 64, "(i64)(short)(st%d_1 & 0xffff)", jc);
-      snprintf(b3, 64, "(i64)(short)(st%d_1 >> 16)", jc);
+/* stage_write: the staged registers, converted, into the LDS image */
+static void emit_stage_write(Gen &g, const char *ind) {
+  std::string &o = g.o;
+  for (int c = 0; c < g.s.NC; c++) {
+    const JitKind &K = jit_kind(g.kinds[c]);
+    if (K.conv == CV_BITS64) {
+      emitf(o, "%s((double2_t *)sval[%d])[tid] = st%d_0;\n", ind, c, c);
+      emitf(o, "%s((double2_t *)sval[%d])[tid + WG] = st%d_1;\n", ind, c, c);
+      continue;
     }
-    emit_lut_probe(b0, "spay[2 * tid]", "        ");
-    emit_lut_probe(b1, "spay[2 * tid + 1]", "        ");
-    emit_lut_probe(b2, "spay[2 * (tid + WG)]", "        ");
-    emit_lut_probe(b3, "spay[2 * (tid + WG) + 1]", "        ");
-  }
-  emit_write("        ");
-  if (fold_preds) {
-    /* evaluate every predicate from the staged registers, one wave ballot
-     * per register row into the chunk bitmap */
-    for (int j = 0; j < 4; j++) {
-      emitf(o, "        { int okp = 1;\n");
-      for (int i = 0; i < p->npreds_d; i++) {
-        emitf(o, "          { const double x = %s;\n"
-                 "            okp &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n",
-              rexpr(p->preds_d[i].cslot, j).c_str(), i, i);
-      }
-      for (int i = 0; i < p->npreds_i; i++) {
-        emitf(o, "          { const i64 x = %s;\n"
-                 "            okp &= (x >= pi%d_lo) & (x <= pi%d_hi); }\n",
-              kexpr_reg(p->preds_i[i].cslot, j).c_str(), i, i);
-      }
-      const int w0 = (j >= 2 ? 1 : 0);   /* +4 blocks for st_1 rows */
-      emitf(o, "          const u64 bl = __ballot(okp);\n"
-               "          if ((tid & 63) == 0) sbits[((tid >> 6) + %d) * 2 + %d] = bl;\n"
-               "        }\n", w0 * 4, j & 1);
+    std::string y[2], st[2];
+    for (int h = 0; h < 2; h++) {
+      y[h] = strf("double2_t y%d; y%d.x = %s; y%d.y = %s;", h, h,
+                  kind_image_from_reg(K, c, 2 * h).c_str(), h,
+                  kind_image_from_reg(K, c, 2 * h + 1).c_str());
+      st[h] = strf("((double2_t *)sval[%d])[tid%s] = y%d;", c,
+                   h ? " + WG" : "", h);
     }
+    emitf(o, "%s{ ", ind);
+    if (K.conv == CV_F32)
+      emitf(o, "float2_t f0 = *(float2_t *)&st%d_0, f1 = *(float2_t *)&st%d_1;\n%s  ",
+            c, c, ind);
+    if (K.store_each)
+      emitf(o, "%s\n%s  %s\n%s  %s\n%s  %s }\n", y[0].c_str(), ind,
+            st[0].c_str(), ind, y[1].c_str(), ind, st[1].c_str());
+    else
+      emitf(o, "%s\n%s  %s\n%s  %s\n%s  %s }\n", y[0].c_str(), ind,
+            y[1].c_str(), ind, st[0].c_str(), ind, st[1].c_str());
   }
-  o += "      } else {\n"
-       "        /* scalar tail conversion (the [rows, CHUNK) image tail is\n"
+}
+
+/* tail / unstaged chunk: convert straight from global memory */
+static void emit_scalar_tail(Gen &g) {
+  std::string &o = g.o;
+  o += "        /* scalar tail conversion (the [rows, CHUNK) image tail is\n"
        "         * zeroed below: raw LDS can hold NaN-pattern bits from the\n"
        "         * previous kernel, and fma(0, NaN, sum) = NaN would poison\n"
        "         * the slot-predicated register accumulators) */\n";
-  if (fold_preds)
-    o += "        for (int i = tid; i < 16; i += WG) sbits[i] = 0ull;\n"
-         "        __syncthreads();\n";
-  for (int c = 0; c < NC; c++) {
-    int k = kinds[c];
-    emitf(o, "        for (int r = tid; r < rows; r += WG) sval[%d][r] = ", c);
-    switch (k) {
-      case SN_K_F64:
-        emitf(o, "((const GAS double *)(body%d))[base + r];\n", c); break;
-      case SN_K_I64:
-        emitf(o, "((const GAS double *)(body%d))[base + r];\n", c); break; /* raw bits */
-      case SN_K_I32:
-        emitf(o, "(double)((const GAS int *)(body%d))[base + r];\n", c); break;
-      case SN_K_F32:
-        emitf(o, "(double)((const GAS float *)(body%d))[base + r];\n", c); break;
-      case SN_K_DICT32:
-        emitf(o, "(double)dm%d[((const GAS int *)(body%d))[base + r]];\n", c, c); break;
-      case SN_K_DICT16:
-        emitf(o, "(double)dm%d[(int)((const GAS unsigned short *)(body%d))[base + r]];\n", c, c); break;
-      default: /* I16 */
-        emitf(o, "(double)((const GAS short *)(body%d))[base + r];\n", c); break;
-    }
-  }
-  for (int c = 0; c < NC; c++)
+  for (int c = 0; c < g.s.NC; c++)
+    emitf(o, "        for (int r = tid; r < rows; r += WG) sval[%d][r] = %s;\n",
+          c, kind_image_from_mem(jit_kind(g.kinds[c]), c).c_str());
+  for (int c = 0; c < g.s.NC; c++)
     emitf(o, "        for (int r = rows + tid; r < CHUNK; r += WG)"
              " sval[%d][r] = 0.0;\n", c);
-  if (fold_preds) {
-    /* same thread wrote these sval rows above — no barrier needed */
-    o += "        for (int r = tid; r < rows; r += WG) {\n"
-         "          int okp = 1;\n";
-    for (int i = 0; i < p->npreds_d; i++)
-      emitf(o, "          { const double x = sval[%d][r];\n"
-               "            okp &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n",
-            p->preds_d[i].cslot, i, i);
-    for (int i = 0; i < p->npreds_i; i++)
-      emitf(o, "          { const i64 x = __double_as_longlong(sval[%d][r]);\n"
-               "            okp &= (x >= pi%d_lo) & (x <= pi%d_hi); }\n",
-            p->preds_i[i].cslot, i, i);
-    o += "          if (okp)\n"
-         "            atomicOr(&sbits[((r >> 7) << 1) | (r & 1)],\n"
-         "                     1ull << ((r >> 1) & 63));\n"
-         "        }\n";
-  }
-  o += "      }\n"
-       "      __syncthreads();\n"
-       "      const int nbase = base + CHUNK;\n"
-       "      const int next_staged = nbase + CHUNK <= tile_end;\n"
-       "      if (next_staged) {\n";
-  emit_load("nbase", "        ");
-  o += "      }\n";
+}
 
-  /* tail / unstaged chunks: fill spay from the LDS image (lane-local
-   * mapping, so no extra barrier before the row pass reads it) */
-  if (use_spay) {
-    int is_i64 = (p->i64_mask >> p->jcslot) & 1u;
-    emitf(o, "      if (!staged) {\n"
-             "#pragma unroll\n"
-             "        for (int k = 0; k < CHUNK / WG; k++) {\n"
-             "          const int r = tid + k * WG;\n"
-             "          const double jx = sval[%d][r];\n",
-          p->jcslot);
-    std::string kx = is_i64 ? "__double_as_longlong(jx)" : "(i64)jx";
-    emit_lut_probe(kx, "spay[r]", "          ");
-    o += "        }\n"
+/* one dense-LUT lookup: dst = payload of kexpr, or -1 outside the span */
+static void emit_lut_probe(Gen &g, const std::string &kexpr,
+                           const std::string &dst, const char *ind) {
+  const sn_dev_plan *p = g.p;
+  emitf(g.o, "%s{ const i64 key = %s;\n"
+           "%s  const int inr = (key >= %lldll) & (key <= %lldll);\n"
+           "%s  const i64 ck = key < %lldll ? %lldll : (key > %lldll ? %lldll : key);\n"
+           "%s  const int pv = jlut[ck - %lldll];\n"
+           "%s  %s = inr ? pv : -1; }\n",
+        ind, kexpr.c_str(),
+        ind, (long long)p->jlut_min, (long long)p->jlut_max,
+        ind, (long long)p->jlut_min, (long long)p->jlut_min,
+        (long long)p->jlut_max, (long long)p->jlut_max,
+        ind, (long long)p->jlut_min,
+        ind, dst.c_str());
+}
+
+/* LUT probe straight from the staged key registers, BEFORE they are
+ * written to LDS: the dependent LUT gathers then overlap the stage_write
+ * + barrier + next stage_load instead of stalling the row pass
+ * (measured: in-pass probing leaves 35% of wave cycles parked).
+ * Register mapping: st_0 covers rows 2*tid(+1), st_1 rows 2*(tid+WG)(+1);
+ * the row pass reads spay[tid + k*WG] after the barrier. */
+static void emit_spay_from_regs(Gen &g) {
+  const int jc = g.p->jcslot;
+  static const char *const dst[4] = { "spay[2 * tid]", "spay[2 * tid + 1]",
+                                      "spay[2 * (tid + WG)]",
+                                      "spay[2 * (tid + WG) + 1]" };
+  for (int j = 0; j < 4; j++)
+    emit_lut_probe(g, kind_key_from_reg(jit_kind(g.kinds[jc]), jc, j,
+                                        plan_col_is_i64(g.p, jc)),
+                   dst[j], "        ");
+}
+
+/* tail / unstaged chunks: fill spay from the LDS image (lane-local
+ * mapping, so no extra barrier before the row pass reads it) */
+static void emit_spay_from_image(Gen &g) {
+  emitf(g.o, "      if (!staged) {\n"
+           "#pragma unroll\n"
+           "        for (int k = 0; k < CHUNK / WG; k++) {\n"
+           "          const int r = tid + k * WG;\n"
+           "          const double jx = sval[%d][r];\n",
+        g.p->jcslot);
+  emit_lut_probe(g, plan_col_is_i64(g.p, g.p->jcslot)
+                        ? "__double_as_longlong(jx)" : "(i64)jx",
+                 "spay[r]", "          ");
+  g.o += "        }\n"
          "      }\n";
-  }
+}
 
-  /* fused row pass */
-  if (fold_preds)
-    o += "#pragma unroll 2\n"
-         "      for (int k = 0; k < CHUNK / WG; k++) {\n"
-         "        const int r = tid + k * WG;\n"
-         "        int ok = (int)((sbits[((r >> 7) << 1) | (r & 1)]\n"
-         "                        >> ((r >> 1) & 63)) & 1ull);\n";
-  else {
-    if (radix_mode) {
-      /* per-k register stash: pass A computes (partition, rank, key,
-       * values) per row; pass B scatters after the per-chunk base
-       * reservation.  Fully unrolled so the arrays stay in registers. */
-      emitf(o, "      i64 rkey[CHUNK / WG];\n"
-               "      int rok[CHUNK / WG], rpk[CHUNK / WG], rrnk[CHUNK / WG];\n");
-      for (int a = 0; a < NA; a++)
-        emitf(o, "      double rva%d[CHUNK / WG];\n", a);
-      o += "#pragma unroll\n";
-    } else {
-      o += "#pragma unroll 2\n";
-    }
-    o += "      for (int k = 0; k < CHUNK / WG; k++) {\n"
-         "        const int r = tid + k * WG;\n"
-         "        int ok = r < rows;\n";
-  }
-  if (has_del)
+/* radix pass A state.  per-k register stash: pass A computes (partition,
+ * rank, key, values) per row; pass B scatters after the per-chunk base
+ * reservation.  Fully unrolled so the arrays stay in registers. */
+static void emit_radix_stash(Gen &g) {
+  emitf(g.o, "      i64 rkey[CHUNK / WG];\n"
+           "      int rok[CHUNK / WG], rpk[CHUNK / WG], rrnk[CHUNK / WG];\n");
+  for (int a = 0; a < g.s.NA; a++)
+    emitf(g.o, "      double rva%d[CHUNK / WG];\n", a);
+}
+
+/* row predicates: delete mask, range predicates, bitmap IN-lists */
+static void emit_row_predicates(Gen &g) {
+  std::string &o = g.o;
+  const sn_dev_plan *p = g.p;
+  if (g.has_del)
     o += "        if (del) {\n"
          "          const int gr = base + r;\n"
          "          ok &= (int)(~(del[(u64)gr >> 6] >> (gr & 63)) & 1ull);\n"
          "        }\n";
-  if (!fold_preds) {
-    for (int i = 0; i < p->npreds_d; i++) {
-      emitf(o, "        { const double x = sval[%d][r];\n"
-               "          ok &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n",
-            p->preds_d[i].cslot, i, i);
-    }
-    for (int i = 0; i < p->npreds_i; i++) {
-      emitf(o, "        { const i64 x = __double_as_longlong(sval[%d][r]);\n"
-               "          ok &= (x >= pi%d_lo) & (x <= pi%d_hi); }\n",
-            p->preds_i[i].cslot, i, i);
-    }
+  for (int i = 0; i < p->npreds_d; i++) {
+    emitf(o, "        { const double x = sval[%d][r];\n"
+             "          ok &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n",
+          p->preds_d[i].cslot, i, i);
+  }
+  for (int i = 0; i < p->npreds_i; i++) {
+    emitf(o, "        { const i64 x = __double_as_longlong(sval[%d][r]);\n"
+             "          ok &= (x >= pi%d_lo) & (x <= pi%d_hi); }\n",
+          p->preds_i[i].cslot, i, i);
   }
   for (int i = 0; i < p->npreds_in && i < 2; i++) {
     const int cs = p->inp[i].cslot;
-    const int is64 = (p->i64_mask >> cs) & 1u;
+    const int is64 = plan_col_is_i64(p, cs);
     emitf(o, "        { const i64 v = %ssval[%d][r]%s;\n"
              "          const i64 ix = v - inb%d_base;\n"
              "          ok &= (ix >= 0) & (ix < inb%d_lim) &\n"
@@ -924,15 +782,19 @@ __device__ __forceinline__ u64 mix64(u64 x) {
           is64 ? "__double_as_longlong(" : "(i64)", cs, is64 ? ")" : "",
           i, i, i);
   }
-  if (radix_mode)   /* before the wave skip: pass B keys off rok alone */
-    o += "        rok[k] = ok;\n";
-  o += "        if (__popcll(__ballot(ok)) == 0) continue;\n";
-  if (p->jkeys) {
-    /* broadcast-dimension probe with literal table shape (mask, key slot,
-     * i64-ness); empty-slot sentinel = INT64_MIN, same as the interpreted
-     * probe_sweep */
-    int is_i64 = (p->i64_mask >> p->jcslot) & 1u;
-    if (slut_mode) {
+}
+
+/* broadcast-dimension probe with literal table shape (mask, key slot,
+ * i64-ness); empty-slot sentinel = INT64_MIN, same as the interpreted
+ * probe_sweep */
+static void emit_join_probe(Gen &g) {
+  std::string &o = g.o;
+  const sn_dev_plan *p = g.p;
+  const char *key = plan_col_is_i64(p, p->jcslot) ? "__double_as_longlong(jx)"
+                                                  : "(i64)jx";
+  switch (g.s.probe) {
+    case PROBE_NONE: break;
+    case PROBE_SLUT:
       /* 4-bit LDS probe: range check + one LDS read per row */
       emitf(o, "        int pay = -1;\n"
                "        {\n"
@@ -946,13 +808,14 @@ __device__ __forceinline__ u64 mix64(u64 x) {
                "          }\n"
                "        }\n"
                "        ok &= pay >= 0;\n",
-            p->jcslot, is_i64 ? "__double_as_longlong(jx)" : "(i64)jx",
-            (long long)p->jlut_min, slut_span);
-    } else if (p->jlut) {
-      (void)is_i64;   /* probed from the staged registers into spay */
+            p->jcslot, key, (long long)p->jlut_min, g.s.slut_span);
+      break;
+    case PROBE_SPAY:
+      /* probed from the staged registers into spay */
       o += "        const int pay = spay[r];\n"
            "        ok &= pay >= 0;\n";
-    } else {
+      break;
+    case PROBE_HASH:
       emitf(o, "        int pay = -1;\n"
                "        if (ok) {\n"
                "          const double jx = sval[%d][r];\n"
@@ -966,26 +829,36 @@ __device__ __forceinline__ u64 mix64(u64 x) {
                "          }\n"
                "          ok = pay >= 0;\n"
                "        }\n",
-            p->jcslot,
-            is_i64 ? "__double_as_longlong(jx)" : "(i64)jx",
+            p->jcslot, key,
             (1u << p->jcap_log2) - 1, (1u << p->jcap_log2) - 1);
-    }
+      break;
   }
-  if (sparse_mode) {
-    /* open-address probe (ByteBufferHashMap.putBufferIfAbsent shape):
-     * key geometry is compile-time, capacity tokenized */
-    if (p->ngroup == 1) {
-      if ((p->i64_mask >> p->gcol[0]) & 1u)
-        emitf(o, "        const i64 skey = __double_as_longlong(sval[%d][r]);\n",
-              p->gcol[0]);
-      else
-        emitf(o, "        const i64 skey = (i64)sval[%d][r];\n", p->gcol[0]);
-    } else {
-      emitf(o, "        const i64 skey = (i64)(((u64)(unsigned)(int)sval[%d][r]"
-               " << 32) | (unsigned)(int)sval[%d][r]);\n",
-            p->gcol[0], p->gcol[1]);
-    }
-    if (radix_mode) {
+}
+
+/* sparse group key: key geometry is compile-time */
+static void emit_sparse_key(Gen &g) {
+  const sn_dev_plan *p = g.p;
+  if (p->ngroup == 1) {
+    if (plan_col_is_i64(p, p->gcol[0]))
+      emitf(g.o, "        const i64 skey = __double_as_longlong(sval[%d][r]);\n",
+            p->gcol[0]);
+    else
+      emitf(g.o, "        const i64 skey = (i64)sval[%d][r];\n", p->gcol[0]);
+  } else {
+    emitf(g.o, "        const i64 skey = (i64)(((u64)(unsigned)(int)sval[%d][r]"
+             " << 32) | (unsigned)(int)sval[%d][r]);\n",
+          p->gcol[0], p->gcol[1]);
+  }
+}
+
+/* the row's accumulator slot */
+static void emit_slot(Gen &g) {
+  std::string &o = g.o;
+  const sn_dev_plan *p = g.p;
+  switch (g.s.slot) {
+    case SLOT_NONE: break;
+    case SLOT_RADIX_RANK:
+      emit_sparse_key(g);
       /* pass A: partition by mix64 HIGH bits (pass 2 probes the segment
        * with the LOW bits — independent), rank via the LDS histogram */
       o += "        rkey[k] = skey;\n"
@@ -995,7 +868,11 @@ __device__ __forceinline__ u64 mix64(u64 x) {
            "          rrnk_ = atomicAdd(&phist[rpk_], 1);\n"
            "        }\n"
            "        rpk[k] = rpk_; rrnk[k] = rrnk_;\n";
-    } else {
+      break;
+    case SLOT_SPARSE_PROBE:
+      /* open-address probe (ByteBufferHashMap.putBufferIfAbsent shape):
+       * capacity tokenized */
+      emit_sparse_key(g);
       o += R"(        int slot = -1;
         if (ok) {
           if (skey == -1ll) slot = hcap;     /* sentinel-valued key */
@@ -1018,9 +895,8 @@ __device__ __forceinline__ u64 mix64(u64 x) {
         }
         ok &= slot >= 0;
 )";
-    }
-  } else if (grouped) {
-    if (p->jkeys && p->jmode == 1) {
+      break;
+    case SLOT_JOIN_ATTR:
       if (p->jslot_mul > 0 && p->ngroup >= 1)
         /* composite GROUP BY dim_attr, fact_col (all literals) */
         emitf(o, "        const int slot = (pay > 0 ? pay : 0) * %d +"
@@ -1028,10 +904,12 @@ __device__ __forceinline__ u64 mix64(u64 x) {
               p->jslot_mul, p->gcol[0], (long long)p->gbase[0]);
       else
         o += "        const int slot = pay > 0 ? pay : 0;\n";
-    } else if (p->ngroup == 0) {
+      break;
+    case SLOT_SINGLE:
       /* keyless plan in the grouped (pac) layout: one slot */
       o += "        const int slot = 0;\n";
-    } else {
+      break;
+    case SLOT_DENSE:
       /* slot = (v0 - base0)*mul0 + (v1 - base1), all literals; dictionary
        * keys arrive premultiplied (base 0, mul 1) so this folds to the
        * plain cast for them */
@@ -1040,190 +918,263 @@ __device__ __forceinline__ u64 mix64(u64 x) {
       if (p->ngroup >= 2)
         emitf(o, "        slot += (int)((i64)sval[%d][r] - %lldll);\n",
               p->gcol[1], (long long)p->gbase[1]);
-    }
+      break;
   }
+}
+
+/* va<a>: each aggregate's input value for this row */
+static void emit_agg_values(Gen &g) {
+  std::string &o = g.o;
   /* factor read: i64 slots hold raw bits in the LDS image — emit the
    * convert only for those slots (compile-time; i64_mask is in the shape) */
-  auto fread = [&](char *dst, int cs) {
-    if ((p->i64_mask >> cs) & 1u)
-      snprintf(dst, 72, "(double)__double_as_longlong(sval[%d][r])", cs);
-    else
-      snprintf(dst, 72, "sval[%d][r]", cs);
+  auto factor = [&](int a, int i, int cs, double fa, double fm) {
+    const std::string f = plan_col_is_i64(g.p, cs)
+        ? strf("(double)__double_as_longlong(sval[%d][r])", cs)
+        : strf("sval[%d][r]", cs);
+    if (ftriv(fa, fm)) return f;
+    return strf("__builtin_fma(ag%d_m%d, %s, ag%d_a%d)", a, i, f.c_str(), a, i);
   };
-  for (int a = 0; a < NA; a++) {
-    const sn_dev_agg &A = p->aggs[a];
+  for (int a = 0; a < g.s.NA; a++) {
+    const sn_dev_agg &A = g.p->aggs[a];
     if (A.nf < 1) { emitf(o, "        const double va%d = 1.0;\n", a); continue; }
-    char t0[128], t1[128], t2[128], f0[72], f1[72], f2[72];
-    fread(f0, A.c0); fread(f1, A.c1); fread(f2, A.c2);
-    if (ftriv(A.a0, A.m0)) snprintf(t0, 128, "%s", f0);
-    else snprintf(t0, 128, "__builtin_fma(ag%d_m0, %s, ag%d_a0)", a, f0, a);
-    if (ftriv(A.a1, A.m1)) snprintf(t1, 128, "%s", f1);
-    else snprintf(t1, 128, "__builtin_fma(ag%d_m1, %s, ag%d_a1)", a, f1, a);
-    if (ftriv(A.a2, A.m2)) snprintf(t2, 128, "%s", f2);
-    else snprintf(t2, 128, "__builtin_fma(ag%d_m2, %s, ag%d_a2)", a, f2, a);
-    emitf(o, "        const double va%d = %s", a, t0);
-    if (A.nf >= 2) emitf(o, " * %s", t1);
-    if (A.nf >= 3) emitf(o, " * %s", t2);
+    emitf(o, "        const double va%d = %s", a,
+          factor(a, 0, A.c0, A.a0, A.m0).c_str());
+    if (A.nf >= 2) emitf(o, " * %s", factor(a, 1, A.c1, A.a1, A.m1).c_str());
+    if (A.nf >= 3) emitf(o, " * %s", factor(a, 2, A.c2, A.a2, A.m2).c_str());
     o += ";\n";
   }
-  if (radix_mode) {
-    for (int a = 0; a < NA; a++)
-      emitf(o, "        rva%d[k] = va%d;\n", a, a);
-  } else if (lds_mode || glob_mode) {
-    emitf(o, "        if (ok) {\n"
-             "          %sdouble *row = &gacc[(u64)slot * %d];\n"
-             "          atomicAdd((double *)&row[%d], 1.0);\n",
-          glob_mode ? "GAS " : "", NA1, NA1 - 1);
-    for (int a = 0; a < NA; a++) {
-      const int op = p->aggs[a].op;
-      if (op == 0)
-        emitf(o, "          atomicAdd((double *)&row[%d], va%d);\n", a, a);
-      else
-        emitf(o, "          %s((unsigned long long *)&row[%d], f64ord(va%d));\n",
-              op == 1 ? "atomicMin" : "atomicMax", a, a);
-      if (pac_mode)
-        emitf(o, "          atomicAdd((double *)&row[%d], 1.0);\n", NA + a);
-    }
-    o += "        }\n";
-  } else if (wbin_mode) {
-    emitf(o, "        if (ok) {\n"
-             "          double *row = &wbin[tid >> 4][slot * %d];\n"
-             "          atomicAdd(&row[%d], 1.0);\n", NA + 1, NA);
-    for (int a = 0; a < NA; a++)
-      emitf(o, "          atomicAdd(&row[%d], va%d);\n", a, a);
-    o += "        }\n";
-  } else if (grouped) {
-    /* m is 0.0 or 1.0; fma(m, va, sum) is bit-identical to the select+add
-     * form (m=0 -> sum exactly, m=1 -> one rounding like the add) but one
-     * VALU op per aggregate instead of two */
-    emitf(o, "#pragma unroll\n        for (int s = 0; s < %d; s++) {\n"
-             "          const double m = (ok && slot == s) ? 1.0 : 0.0;\n"
-             "          rc[s] += m;\n", NS);
-    for (int a = 0; a < NA; a++) {
-      const int op = p->aggs[a].op;
-      if (op == 0)
-        emitf(o, "          sums[s][%d] = __builtin_fma(m, va%d, sums[s][%d]);\n",
-              a, a, a);
-      else
-        emitf(o, "          sums[s][%d] = %s(sums[s][%d],\n"
-                 "              (ok && slot == s) ? va%d : __longlong_as_double(%s));\n",
-              a, op == 1 ? "fmin" : "fmax", a, a,
-              op == 1 ? "0x7FF0000000000000ll" : "0xFFF0000000000000ll");
-    }
-    o += "        }\n";
-  } else {
-    for (int a = 0; a < NA; a++) {
-      emitf(o, "        sums[%d] += ok ? va%d : 0.0;\n", a, a);
-      emitf(o, "        cnts[%d] += ok ? 1.0 : 0.0;\n", a);
-    }
-    o += "        rcnt += ok ? 1.0 : 0.0;\n";
+}
+
+/* the row's values into the accumulator the mode keeps */
+static void emit_accumulate(Gen &g) {
+  std::string &o = g.o;
+  const JitShape &s = g.s;
+  switch (s.acc) {
+    case ACC_RADIX:   /* stashed for the scatter */
+      for (int a = 0; a < s.NA; a++)
+        emitf(o, "        rva%d[k] = va%d;\n", a, a);
+      break;
+    case ACC_SPARSE: case ACC_GLOBAL: case ACC_LDS:
+      /* atomics into the row of gacc (HBM, or LDS) that `slot` names */
+      emitf(o, "        if (ok) {\n"
+               "          %sdouble *row = &gacc[(u64)slot * %d];\n"
+               "          atomicAdd((double *)&row[%d], 1.0);\n",
+            s.acc == ACC_LDS ? "" : "GAS ", s.NA1, s.NA1 - 1);
+      for (int a = 0; a < s.NA; a++) {
+        const int op = g.p->aggs[a].op;
+        if (op == 0)
+          emitf(o, "          atomicAdd((double *)&row[%d], va%d);\n", a, a);
+        else
+          emitf(o, "          %s((unsigned long long *)&row[%d], f64ord(va%d));\n",
+                op == 1 ? "atomicMin" : "atomicMax", a, a);
+        if (g.p->pac)
+          emitf(o, "          atomicAdd((double *)&row[%d], 1.0);\n", s.NA + a);
+      }
+      o += "        }\n";
+      break;
+    case ACC_WBIN:
+      emitf(o, "        if (ok) {\n"
+               "          double *row = &wbin[tid >> 4][slot * %d];\n"
+               "          atomicAdd(&row[%d], 1.0);\n", s.NA + 1, s.NA);
+      for (int a = 0; a < s.NA; a++)
+        emitf(o, "          atomicAdd(&row[%d], va%d);\n", a, a);
+      o += "        }\n";
+      break;
+    case ACC_REGS:
+      /* m is 0.0 or 1.0; fma(m, va, sum) is bit-identical to the select+add
+       * form (m=0 -> sum exactly, m=1 -> one rounding like the add) but one
+       * VALU op per aggregate instead of two */
+      emitf(o, "#pragma unroll\n        for (int s = 0; s < %d; s++) {\n"
+               "          const double m = (ok && slot == s) ? 1.0 : 0.0;\n"
+               "          rc[s] += m;\n", s.NS);
+      for (int a = 0; a < s.NA; a++) {
+        const int op = g.p->aggs[a].op;
+        if (op == 0)
+          emitf(o, "          sums[s][%d] = __builtin_fma(m, va%d, sums[s][%d]);\n",
+                a, a, a);
+        else
+          emitf(o, "          sums[s][%d] = %s(sums[s][%d],\n"
+                   "              (ok && slot == s) ? va%d : __longlong_as_double(%s));\n",
+                a, op == 1 ? "fmin" : "fmax", a, a,
+                op == 1 ? "0x7FF0000000000000ll" : "0xFFF0000000000000ll");
+      }
+      o += "        }\n";
+      break;
+    case ACC_KEYLESS:
+      for (int a = 0; a < s.NA; a++) {
+        emitf(o, "        sums[%d] += ok ? va%d : 0.0;\n", a, a);
+        emitf(o, "        cnts[%d] += ok ? 1.0 : 0.0;\n", a);
+      }
+      o += "        rcnt += ok ? 1.0 : 0.0;\n";
+      break;
   }
+}
+
+/* radix pass B: reserve contiguous global space per (chunk, partition) —
+ * one global atomic per NON-EMPTY partition per chunk, not one per row —
+ * then scatter the stashed records to [base, base+count) */
+static void emit_radix_scatter(Gen &g) {
+  std::string &o = g.o;
+  emitf(o, "      __syncthreads();\n"
+           "      for (int i = tid; i < npart; i += WG) {\n"
+           "        const int c = phist[i];\n"
+           "        phist[i] = c ? atomicAdd(&pcount[i], c) : 0;\n"
+           "      }\n"
+           "      __syncthreads();\n"
+           "#pragma unroll\n"
+           "      for (int k = 0; k < CHUNK / WG; k++) {\n"
+           "        if (!rok[k]) continue;\n"
+           "        const u64 off = (u64)phist[rpk[k]] + (u64)rrnk[k];\n"
+           "        if (off >= (u64)percap) { atomicOr(hflags + 3, 1); continue; }\n"
+           "        GAS double *rec = precs + ((u64)rpk[k] * (u64)percap + off) * %d;\n"
+           "        ((GAS i64 *)rec)[0] = rkey[k];\n", 1 + g.s.NA);
+  for (int a = 0; a < g.s.NA; a++)
+    emitf(o, "        rec[%d] = rva%d[k];\n", 1 + a, a);
   o += "      }\n";
-  if (radix_mode) {
-    /* reserve contiguous global space per (chunk, partition) — one global
-     * atomic per NON-EMPTY partition per chunk, not one per row — then
-     * scatter the stashed records to [base, base+count) */
-    emitf(o, "      __syncthreads();\n"
-             "      for (int i = tid; i < npart; i += WG) {\n"
-             "        const int c = phist[i];\n"
-             "        phist[i] = c ? atomicAdd(&pcount[i], c) : 0;\n"
-             "      }\n"
-             "      __syncthreads();\n"
-             "#pragma unroll\n"
-             "      for (int k = 0; k < CHUNK / WG; k++) {\n"
-             "        if (!rok[k]) continue;\n"
-             "        const u64 off = (u64)phist[rpk[k]] + (u64)rrnk[k];\n"
-             "        if (off >= (u64)percap) { atomicOr(hflags + 3, 1); continue; }\n"
-             "        GAS double *rec = precs + ((u64)rpk[k] * (u64)percap + off) * %d;\n"
-             "        ((GAS i64 *)rec)[0] = rkey[k];\n", 1 + NA);
-    for (int a = 0; a < NA; a++)
-      emitf(o, "        rec[%d] = rva%d[k];\n", 1 + a, a);
-    o += "      }\n";
+}
+
+/* copy a block-level accumulator of nv cells to the block's scratch row */
+static void emit_store_row(Gen &g, const char *cell) {
+  emitf(g.o, "  __syncthreads();\n"
+           "  for (int i = tid; i < %d; i += WG)\n"
+           "    out[(u64)blockIdx.x * %d + i] = %s;\n", g.s.nv, g.s.nv, cell);
+}
+
+/* after the tile loop: the block's partials to its scratch row */
+static void emit_flush(Gen &g) {
+  std::string &o = g.o;
+  const JitShape &s = g.s;
+  switch (s.acc) {
+    case ACC_GLOBAL: case ACC_SPARSE: case ACC_RADIX:
+      /* nothing to flush — the HBM accumulator holds the single partial set */
+      break;
+    case ACC_LDS:
+      /* gacc IS the block accumulator — flush it straight to the scratch row */
+      emit_store_row(g, "gacc[i]");
+      break;
+    case ACC_WBIN:
+      emitf(o, "  __syncthreads();\n"
+               "  for (int i = tid; i < %d; i += WG) {\n"
+               "    double acc = 0.0;\n"
+               "#pragma unroll\n"
+               "    for (int w = 0; w < 16; w++) acc += wbin[w][i];\n"
+               "    out[(u64)blockIdx.x * %d + i] = acc;\n"
+               "  }\n", s.nv, s.nv);
+      break;
+    case ACC_REGS:
+      /* block reduce into LDS bacc then scratch row */
+      emit_acc_init(o, g, "bacc", s.nv, s.mm_any);
+      emitf(o, "#pragma unroll\n  for (int s = 0; s < %d; s++) {\n", s.NS);
+      for (int a = 0; a < s.NA; a++) {
+        const int op = g.p->aggs[a].op;
+        if (op == 0)
+          emitf(o, "    { double x = wsum(sums[s][%d]);\n"
+                   "      if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[s * %d + %d], x); }\n",
+                a, s.NA1, a);
+        else
+          emitf(o, "    { double x = %s(sums[s][%d]);\n"
+                   "      if ((tid & 63) == 0)\n"
+                   "        %s((unsigned long long *)&bacc[s * %d + %d], f64ord(x)); }\n",
+                op == 1 ? "wmin" : "wmax", a,
+                op == 1 ? "atomicMin" : "atomicMax", s.NA1, a);
+      }
+      emitf(o, "    { double x = wsum(rc[s]);\n"
+               "      if ((tid & 63) == 0 && x != 0.0) {\n"
+               "        atomicAdd(&bacc[s * %d + %d], x);\n", s.NA1, s.NA1 - 1);
+      if (g.p->pac)
+        for (int a = 0; a < s.NA; a++)
+          emitf(o, "        atomicAdd(&bacc[s * %d + %d], x);\n", s.NA1, s.NA + a);
+      o += "      } }\n  }\n";
+      emit_store_row(g, "bacc[i]");
+      break;
+    case ACC_KEYLESS:
+      emit_acc_init(o, g, "bacc", s.nv, 0);
+      for (int a = 0; a < s.NA; a++) {
+        emitf(o, "  { double x = wsum(sums[%d]);\n"
+                 "    if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[%d], x); }\n", a, a);
+        emitf(o, "  { double x = wsum(cnts[%d]);\n"
+                 "    if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[%d], x); }\n",
+              a, g.na_t + a);
+      }
+      emitf(o, "  { double x = wsum(rcnt);\n"
+               "    if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[%d], x); }\n",
+            2 * g.na_t);
+      emit_store_row(g, "bacc[i]");
+      break;
   }
+  o += "}\n";
+}
+
+/* Generate the specialized kernel source.
+ * kinds[c]: SN_K_* per used column slot (uniform across batches).
+ * Layout contract identical to the interpreted kernels:
+ *   keyless: scratch row [2*na_t+1] = [sums][counts][rowcount]
+ *   grouped: scratch row [nslots*(naggs+1)], rowcount at +naggs.
+ * (Fused register pass, stage-time predicate folding: measured slower and
+ * removed — DESIGN.md, "Built, MEASURED, and reverted".) */
+static std::string gen_source(const sn_dev_plan *p, const int *kinds,
+                              int nslots, int na_t, int has_del) {
+  Gen g = { std::string(), p, kinds, na_t, has_del,
+            jit_classify(p, kinds, nslots, na_t, has_del) };
+  std::string &o = g.o;
+  const bool radix = g.s.acc == ACC_RADIX;
+
+  emit_prelude(o);
+  emit_signature(g);
+  emit_literals(g);
+  emit_acc_decl(g);
+  emit_probe_decl(g);
+  emit_stage_regs(g);
+  if (g.s.probe == PROBE_SLUT) emit_slut_pack(g);
+
+  /* per tile: chunks of CHUNK rows, double-buffered through registers —
+   * chunk n+1's global loads fly while chunk n's row pass runs from LDS */
+  emit_tile_prologue(g);
+  o += "    int staged = 0;\n"
+       "    if (tile.row_start + CHUNK <= tile_end) {\n";
+  emit_stage_load(g, "tile.row_start", "      ");
+  o += "      staged = 1;\n    }\n"
+       "    for (int base = tile.row_start; base < tile_end; base += CHUNK) {\n"
+       "      const int rows = min(CHUNK, tile_end - base);\n";
+  if (radix)   /* previous chunk's scatter is behind the tail barrier */
+    o += "      for (int i = tid; i < npart; i += WG) phist[i] = 0;\n";
+  o += "      if (staged) {\n";
+  if (g.s.probe == PROBE_SPAY) emit_spay_from_regs(g);
+  emit_stage_write(g, "        ");
+  o += "      } else {\n";
+  emit_scalar_tail(g);
+  o += "      }\n"
+       "      __syncthreads();\n"
+       "      const int nbase = base + CHUNK;\n"
+       "      const int next_staged = nbase + CHUNK <= tile_end;\n"
+       "      if (next_staged) {\n";
+  emit_stage_load(g, "nbase", "        ");
+  o += "      }\n";
+  if (g.s.probe == PROBE_SPAY) emit_spay_from_image(g);
+
+  /* row pass: predicates, probe, slot, values and accumulate in one sweep */
+  if (radix) emit_radix_stash(g);
+  o += radix ? "#pragma unroll\n" : "#pragma unroll 2\n";
+  o += "      for (int k = 0; k < CHUNK / WG; k++) {\n"
+       "        const int r = tid + k * WG;\n"
+       "        int ok = r < rows;\n";
+  emit_row_predicates(g);
+  if (radix)   /* before the wave skip: pass B keys off rok alone */
+    o += "        rok[k] = ok;\n";
+  o += "        if (__popcll(__ballot(ok)) == 0) continue;\n";
+  emit_join_probe(g);
+  emit_slot(g);
+  emit_agg_values(g);
+  emit_accumulate(g);
+  o += "      }\n";
+  if (radix) emit_radix_scatter(g);
   o += "      __syncthreads();\n"
        "      staged = next_staged;\n"
        "    }\n"
        "  }\n";
 
-  /* block reduce into LDS bacc then scratch row */
-  int nv = grouped ? NS * NA1 : 2 * na_t + 1;
-  if (glob_mode) {
-    /* nothing to flush — the HBM accumulator holds the single partial set */
-    o += "}\n";
-    return o;
-  }
-  if (lds_mode) {
-    /* gacc IS the block accumulator — flush it straight to the scratch row */
-    emitf(o, "  __syncthreads();\n"
-             "  for (int i = tid; i < %d; i += WG)\n"
-             "    out[(u64)blockIdx.x * %d + i] = gacc[i];\n"
-             "}\n", nv, nv);
-    return o;
-  }
-  if (wbin_mode) {
-    emitf(o, "  __syncthreads();\n"
-             "  for (int i = tid; i < %d; i += WG) {\n"
-             "    double acc = 0.0;\n"
-             "#pragma unroll\n"
-             "    for (int w = 0; w < 16; w++) acc += wbin[w][i];\n"
-             "    out[(u64)blockIdx.x * %d + i] = acc;\n"
-             "  }\n"
-             "}\n", nv, nv);
-    return o;
-  }
-  if (!mm_any || !grouped) {
-    emitf(o, "  for (int i = tid; i < %d; i += WG) bacc[i] = 0.0;\n"
-             "  __syncthreads();\n", nv);
-  } else {
-    emitf(o, "  for (int i = tid; i < %d; i += WG) {\n"
-             "    const int a = i %% %d;\n"
-             "    double iv = 0.0;\n", nv, NA1);
-    for (int a = 0; a < NA; a++)
-      if (p->aggs[a].op != 0)
-        emitf(o, "    if (a == %d) iv = __longlong_as_double(%s);\n", a,
-              p->aggs[a].op == 1 ? "0xFFF8000000000000ll"
-                                 : "0x0000000000000000ll");
-    o += "    bacc[i] = iv;\n  }\n  __syncthreads();\n";
-  }
-  if (grouped) {
-    emitf(o, "#pragma unroll\n  for (int s = 0; s < %d; s++) {\n", NS);
-    for (int a = 0; a < NA; a++) {
-      const int op = p->aggs[a].op;
-      if (op == 0)
-        emitf(o, "    { double x = wsum(sums[s][%d]);\n"
-                 "      if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[s * %d + %d], x); }\n",
-              a, NA1, a);
-      else
-        emitf(o, "    { double x = %s(sums[s][%d]);\n"
-                 "      if ((tid & 63) == 0)\n"
-                 "        %s((unsigned long long *)&bacc[s * %d + %d], f64ord(x)); }\n",
-              op == 1 ? "wmin" : "wmax", a,
-              op == 1 ? "atomicMin" : "atomicMax", NA1, a);
-    }
-    emitf(o, "    { double x = wsum(rc[s]);\n"
-             "      if ((tid & 63) == 0 && x != 0.0) {\n"
-             "        atomicAdd(&bacc[s * %d + %d], x);\n", NA1, NA1 - 1);
-    if (pac_mode)
-      for (int a = 0; a < NA; a++)
-        emitf(o, "        atomicAdd(&bacc[s * %d + %d], x);\n", NA1, NA + a);
-    o += "      } }\n  }\n";
-  } else {
-    for (int a = 0; a < NA; a++) {
-      emitf(o, "  { double x = wsum(sums[%d]);\n"
-               "    if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[%d], x); }\n", a, a);
-      emitf(o, "  { double x = wsum(cnts[%d]);\n"
-               "    if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[%d], x); }\n",
-            a, na_t + a);
-    }
-    emitf(o, "  { double x = wsum(rcnt);\n"
-             "    if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[%d], x); }\n",
-          2 * na_t);
-  }
-  emitf(o, "  __syncthreads();\n"
-           "  for (int i = tid; i < %d; i += WG)\n"
-           "    out[(u64)blockIdx.x * %d + i] = bacc[i];\n"
-           "}\n", nv, nv);
-  return o;
+  emit_flush(g);
+  return std::move(g.o);
 }
 
 /* compile (or fetch) the kernel for this plan; returns NULL on any failure
@@ -1282,14 +1233,6 @@ extern "C" void *sn_jit_get(void *cache, const sn_dev_plan *p,
   mix(&shape, sizeof(shape));
   mix(kinds, sizeof(int) * SN_DEV_MAX_COLS);
   mix(&nslots, 4); mix(&na_t, 4); mix(&has_del, 4);
-  if (getenv("SN_DBG_JIT")) {
-    fprintf(stderr, "[jit] h=%016llx na=%d ns=%d pac=%d sparse=%d ops=",
-            (unsigned long long)h, p->naggs, nslots, p->pac, p->sparse);
-    for (int a = 0; a < p->naggs; a++) fprintf(stderr, "%d", p->aggs[a].op);
-    fprintf(stderr, " nf=");
-    for (int a = 0; a < p->naggs; a++) fprintf(stderr, "%d", p->aggs[a].nf);
-    fprintf(stderr, "\n");
-  }
   {
     std::lock_guard<std::mutex> g(jc->mu);
     auto it = jc->fns.find(h);
