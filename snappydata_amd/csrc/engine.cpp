@@ -1928,8 +1928,6 @@ struct PartialSlot {
 static_assert(sizeof(PartialSlot) == SN_MAX_GROUPS * SN_KEY_MAX + 8 +
               2 * SN_MAX_AGGS * 8 + 8, "partial slot layout");
 
-static int template_naggs(int na) { return na <= 2 ? 2 : na <= 4 ? 4 : na <= 8 ? 8 : 12; }
-
 static bool batch_skippable(const Batch &b, const sn_plan *p, const Table *t) {
   if (!b.stats_valid || b.has_deltas || b.has_deletes) return false;
   for (int i = 0; i < p->npreds; i++) {
@@ -2395,7 +2393,7 @@ static int32_t build_aggs(sn_query *q, sn_dev_plan &dp, bool dec) {
   dp.naggs = q->dev_naggs;
   for (int a = 0; a < q->dev_naggs; a++)
     if (dp.aggs[a].op != 0) q->mm = true;
-  q->na_t = template_naggs(q->dev_naggs > 0 ? q->dev_naggs : 1);
+  q->na_t = sn_na_t(q->dev_naggs);
   q->out_stride = 2 * (size_t)q->na_t + 1;
   return SN_OK;
 }
@@ -2564,14 +2562,6 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out
 }
 
 /* ---- launch helpers ---- */
-
-/* grid of a query-compiled scan: one block per tile up to the cap, then
- * balanced rounds */
-static int jit_grid(int32_t ntiles) {
-  if (ntiles <= SN_GRID_CAP) return ntiles;
-  int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
-  return (ntiles + rounds - 1) / rounds;
-}
 
 /* IN-lists run compiled only in bitmap form (sorted-list search stays
  * interpreted) */
@@ -2846,7 +2836,7 @@ static int32_t launch_sparse(sn_query *q, const sn_dev_plan &dp,
     if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
     int rc = -1;
     if (jfn) {
-      rc = sn_jit_launch(jfn, jit_grid(set.ntiles),
+      rc = sn_jit_launch(jfn, sn_balanced_grid(set.ntiles, SN_GRID_CAP),
                          (const sn_dev_batch *)set.db_dev,
                          (const sn_dev_tile *)set.tl_dev, set.ntiles,
                          e->hws_acc, (const int64_t *)e->hws_keys,
@@ -2940,24 +2930,19 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
   if (ntiles == 0) return SN_OK;
   void *dp_dev = cached_dev_plan(e, dp);
   if (!dp_dev) return fail(SN_ERR_NOMEM, "plan upload");
-  /* block-partial scratch rows (the >16-slot path caps its grid) */
-  int grid = ntiles < SN_GRID_CAP ? ntiles : SN_GRID_CAP;
-  if (dp.nslots > 16 && grid > SN_GRID_BIGSLOT) grid = SN_GRID_BIGSLOT;
-  const int na1 = dp.pac ? 2 * q->dev_naggs + 1 : q->dev_naggs + 1;
-  size_t nv = (dp.nslots <= 1 && !dp.pac)
-                  ? (size_t)(2 * q->na_t + 1)
-                  : (size_t)(dp.nslots < 1 ? 1 : dp.nslots) * na1;
-  const bool big_groups =
-      dp.nslots > SN_RESULT_PAGE ||
-      (dp.pac && sn_grouped_needs_global(dp.nused, dp.nslots, na1));
-  int rc = ensure_scratch(e, (big_groups ? 8 : (size_t)grid) * nv * 8);
+  /* one description of the launch, shared with sn_launch_scan_agg: scratch
+   * holds the partial rows of whichever twin runs (interpreted or
+   * compiled), or the 8 XCD-private copies of a global accumulator */
+  const sn_dense_launch d = sn_dense_launch_of(&dp, ntiles);
+  const size_t rows = (size_t)std::max(sn_dense_rows(&d, 0), sn_dense_rows(&d, 1));
+  int rc = ensure_scratch(e, rows * d.nv * 8);
   if (rc != SN_OK) return rc;
-  if (big_groups &&
-      hipMemsetAsync(e->scratch, 0, 8 * nv * 8, e->stream) != hipSuccess)
+  if (d.global_acc &&
+      hipMemsetAsync(e->scratch, 0, rows * d.nv * 8, e->stream) != hipSuccess)
     return fail(SN_ERR_GENERIC, "accumulator zero");
-  if (big_groups && q->mm &&
-      sn_launch_acc_init(e->scratch, 8ll * dp.nslots, q->dev_naggs, na1,
-                         dp_dev, e->stream) != 0)
+  if (d.global_acc && q->mm &&
+      sn_launch_acc_init(e->scratch, (long long)rows * dp.nslots, q->dev_naggs,
+                         d.na1, dp_dev, e->stream) != 0)
     return fail(SN_ERR_GENERIC, "accumulator min/max init");
   acquire_events(q);
   /* query-compiled kernel (jit.cpp): plan constants baked as literals —
@@ -2971,18 +2956,13 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
   if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
   rc = -1;
   if (jfn) {
-    int jgrid = jit_grid(ntiles);
-    /* >16-slot scratch rows are wide; mirror the interpreted grid cap
-     * (scratch was sized with the same bound above) */
-    if (dp.nslots > 16 && jgrid > SN_GRID_BIGSLOT) jgrid = SN_GRID_BIGSLOT;
-    int naggs1 = (dp.nslots <= 1 && !dp.pac) ? 0 : na1;
-    rc = sn_jit_launch(jfn, jgrid, (const sn_dev_batch *)set.db_dev,
+    rc = sn_jit_launch(jfn, d.grid_compiled, (const sn_dev_batch *)set.db_dev,
                        (const sn_dev_tile *)set.tl_dev, ntiles, e->scratch,
                        dp.jkeys, dp.jpayload, dp.jlut,
                        (const sn_dev_plan *)dp_dev, e->stream);
     if (rc == 0)
-      rc = sn_launch_reduce(e->scratch, big_groups ? 8 : jgrid, (int)nv,
-                            q->dev_out, naggs1, (int)q->out_stride,
+      rc = sn_launch_reduce(e->scratch, sn_dense_rows(&d, 1), d.nv,
+                            q->dev_out, d.naggs1, d.out_stride,
                             dp_dev, e->stream);
     q->used_jit = rc == 0;
     if (rc != 0) jfn = nullptr;   /* interpreted kernels take over */

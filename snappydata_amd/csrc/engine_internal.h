@@ -225,20 +225,6 @@ static inline int sn_radix_direct(int sub_log2, int naggs1) {
 
 #define SN_SCAN_CHUNK 1024     /* rows per LDS conversion chunk (kernels.hip) */
 
-/* shared host/launcher routing predicate: does the grouped LDS-accumulator
- * kernel fit, or must the plan take the global-atomic route?  Used by BOTH
- * sn_launch_scan_agg and the engine (which must zero the global accumulator
- * before launch) so the two can never disagree. */
-static inline int sn_grouped_needs_global(int nused, int nslots, int na1) {
-  unsigned long long lds =
-      (unsigned long long)nused * SN_SCAN_CHUNK * 8 +
-      (unsigned long long)nused * (SN_SCAN_CHUNK / 64) * 8 +
-      2ull * (SN_SCAN_CHUNK / 64) * 8 + sizeof(sn_dev_plan) + 512 +
-      (SN_SCAN_CHUNK / 64) * 8 + SN_SCAN_CHUNK * 2 +
-      (unsigned long long)nslots * na1 * 8 + 64;
-  return lds > 160ull * 1024;
-}
-
 /* ---- exact DECIMAL aggregation (k_dec_keyless / k_dec_grouped) ----
  * Canonical decimal aggregate input: value = f0*f1*f2 with
  * f_i = add[i] + mul[i]*x_i formed in int64 (the host proves no int64 wrap
@@ -268,39 +254,6 @@ typedef struct {
 static inline int sn_dec_row_cells(int naggs) {
   return SN_DEC_ROW_CELLS(naggs);
 }
-/* LDS bytes of the decimal kernels: the shared decode front end's staging
- * image (values, validity, dead/alive words), both plan mirrors, and the
- * per-block accumulator of nslots rows (keyless: nslots == 1). */
-static inline unsigned long long sn_dec_lds_bytes(int nused, int nslots,
-                                                  int naggs) {
-  return (unsigned long long)nused * SN_SCAN_CHUNK * 8 +
-         (unsigned long long)nused * (SN_SCAN_CHUNK / 64) * 8 +
-         2ull * (SN_SCAN_CHUNK / 64) * 8 + 16 +
-         sizeof(sn_dev_plan) + sizeof(sn_dev_dec_plan) +
-         (unsigned long long)nslots * sn_dec_row_cells(naggs) * 8 +
-         4ull * sn_dec_row_cells(naggs) * 8 /* keyless per-wave partials */;
-}
-/* largest dense slot count the decimal grouped kernel admits (160 KiB LDS) */
-static inline int sn_dec_max_slots(int nused, int naggs) {
-  const unsigned long long fixed = sn_dec_lds_bytes(nused, 0, naggs);
-  if (fixed >= 160ull * 1024) return 0;
-  return (int)((160ull * 1024 - fixed) /
-               ((unsigned long long)sn_dec_row_cells(naggs) * 8));
-}
-/* replication factor of the grouped LDS accumulator (lane l updates copy
- * l % copies, so few-group shapes do not serialize a whole wave on one LDS
- * address): the largest power of two <= 16 that keeps a block within half
- * the CU's LDS (two resident blocks), or within all of it when one copy
- * already needs more than half. */
-static inline int sn_dec_copies(int nused, int nslots, int naggs) {
-  const unsigned long long budget =
-      sn_dec_lds_bytes(nused, nslots, naggs) <= 80ull * 1024 ? 80ull * 1024
-                                                             : 160ull * 1024;
-  int c = 1;
-  while (c < 16 && sn_dec_lds_bytes(nused, nslots * c * 2, naggs) <= budget)
-    c *= 2;
-  return c;
-}
 #define SN_DEC_GRID_CAP 512   /* blocks (scratch rows) of a decimal scan */
 
 #define SN_GRID_CAP 2048
@@ -310,6 +263,215 @@ static inline int sn_dec_copies(int nused, int nslots, int naggs) {
 #define SN_GRID_BIGSLOT 256   /* grid cap for the >16-slot LDS hash-agg path */
 #define SN_TILE_ROWS 16384     /* rows per workgroup tile (16 LDS chunks;
                                   long pipelines for the staged conversion) */
+
+#ifdef __HIP__
+#define SN_HD __host__ __device__
+#else
+#define SN_HD
+#endif
+
+/* ---- the scan kernels' dynamic-LDS layout, for kernels and host alike ----
+ * Every scan kernel stages one chunk of each referenced column into the same
+ * image and carves its pointers from sn_lds_layout; every launcher and
+ * routing predicate takes its byte count from the same call, so a kernel and
+ * its launcher cannot disagree on an offset or a size.  Regions, in order:
+ *   sval    [nused][CHUNK] f64 values (offset 0)
+ *   svalid  [nused][CHUNK/64] validity words
+ *   sdead   [CHUNK/64], salive [CHUNK/64]
+ *   sslot   [CHUNK] int16 per-row slot image          (slot_image only)
+ *   plan    sn_dev_plan mirror, then plan2 = any further mirror
+ *   acc     the block accumulator
+ *   slack   unused tail
+ * LDS bytes decide occupancy, the 160 KiB rejections and the LDS-versus-
+ * global routing, so each kernel's historical pad is kept as a named slack
+ * constant instead of being trimmed. */
+#define SN_LDS_LIMIT (160ull * 1024)
+#define SN_LDS_BITMAP (SN_SCAN_CHUNK / 64 * 8)      /* one row bitmap */
+#define SN_LDS_SLOT_IMAGE (SN_SCAN_CHUNK * 2)
+#define SN_LDS_KEYLESS_ACC 512  /* k_keyless block row, 2 * 12 + 1 doubles */
+#define SN_LDS_SLACK_GROUPED (512 + SN_LDS_BITMAP + 16)
+#define SN_LDS_SLACK_LDS (512 + SN_LDS_BITMAP + 64)    /* also k_grouped_reg */
+#define SN_LDS_SLACK_GLOBAL (SN_LDS_SLACK_LDS + sizeof(sn_dev_plan))
+#define SN_LDS_SLACK_HASH 64                           /* also k_join_build */
+#define SN_LDS_SLACK_DEC 16
+#define SN_REG_SLOTS 8          /* k_grouped_reg's slot capacity */
+
+typedef struct {
+  unsigned svalid, sdead, salive, sslot, plan, plan2, acc;  /* byte offsets */
+  unsigned long long total;
+} sn_lds;
+
+static inline SN_HD sn_lds sn_lds_layout(int nused, int slot_image,
+                                         unsigned mirror_bytes,
+                                         unsigned long long acc_bytes,
+                                         unsigned long long slack) {
+  sn_lds l;
+  l.svalid = (unsigned)nused * SN_SCAN_CHUNK * 8;
+  l.sdead = l.svalid + (unsigned)nused * SN_LDS_BITMAP;
+  l.salive = l.sdead + SN_LDS_BITMAP;
+  l.sslot = l.salive + SN_LDS_BITMAP;
+  l.plan = l.sslot + (slot_image ? SN_LDS_SLOT_IMAGE : 0);
+  l.plan2 = l.plan + (unsigned)sizeof(sn_dev_plan);
+  l.acc = l.plan + mirror_bytes;
+  l.total = l.acc + acc_bytes + slack;
+  return l;
+}
+
+/* template roundings: aggregate capacity of the keyless kernels (also the
+ * result stride), slot capacity of k_grouped */
+static inline SN_HD int sn_na_t(int na) {
+  return na <= 2 ? 2 : na <= 4 ? 4 : na <= 8 ? 8 : 12;
+}
+static inline SN_HD int sn_grouped_ns_t(int ns) {
+  return ns <= 4 ? 4 : ns <= 8 ? 8 : 16;
+}
+
+static inline SN_HD sn_lds sn_lds_keyless(int nused) {
+  return sn_lds_layout(nused, 0, sizeof(sn_dev_plan), SN_LDS_KEYLESS_ACC, 0);
+}
+/* acc [ns_t][naggs + 1]: ns_t is the kernel's template slot capacity */
+static inline SN_HD sn_lds sn_lds_grouped(int nused, int ns_t, int naggs) {
+  return sn_lds_layout(nused, 1, sizeof(sn_dev_plan),
+                       (unsigned long long)ns_t * (naggs + 1) * 8,
+                       SN_LDS_SLACK_GROUPED);
+}
+static inline SN_HD sn_lds sn_lds_grouped_lds(int nused, int nslots, int na1) {
+  return sn_lds_layout(nused, 1, sizeof(sn_dev_plan),
+                       (unsigned long long)nslots * na1 * 8, SN_LDS_SLACK_LDS);
+}
+static inline SN_HD sn_lds sn_lds_grouped_reg(int nused, int naggs) {
+  return sn_lds_layout(nused, 0, sizeof(sn_dev_plan),
+                       (unsigned long long)SN_REG_SLOTS * (naggs + 1) * 8,
+                       SN_LDS_SLACK_LDS);
+}
+static inline SN_HD sn_lds sn_lds_grouped_global(int nused) {
+  return sn_lds_layout(nused, 1, sizeof(sn_dev_plan), 0, SN_LDS_SLACK_GLOBAL);
+}
+static inline SN_HD sn_lds sn_lds_hash(int nused) {
+  return sn_lds_layout(nused, 0, sizeof(sn_dev_plan), 0, SN_LDS_SLACK_HASH);
+}
+static inline SN_HD sn_lds sn_lds_join_build(int nused) {
+  return sn_lds_layout(nused, 0, 0, 0, SN_LDS_SLACK_HASH);
+}
+/* decimal kernels: both plan mirrors; acc = nslots accumulator rows
+ * (keyless: one) plus the keyless kernel's four per-wave partial rows */
+static inline SN_HD sn_lds sn_lds_dec(int nused, int nslots, int naggs) {
+  return sn_lds_layout(nused, 0, sizeof(sn_dev_plan) + sizeof(sn_dev_dec_plan),
+                       ((unsigned long long)nslots + 4) *
+                           SN_DEC_ROW_CELLS(naggs) * 8,
+                       SN_LDS_SLACK_DEC);
+}
+
+/* does the grouped LDS-accumulator kernel fit, or must the plan take the
+ * global-atomic route?  Asked by the launcher and by the engine, which must
+ * zero the global accumulator before launch. */
+static inline int sn_grouped_needs_global(int nused, int nslots, int na1) {
+  return sn_lds_grouped_lds(nused, nslots, na1).total > SN_LDS_LIMIT;
+}
+
+static inline unsigned long long sn_dec_lds_bytes(int nused, int nslots,
+                                                  int naggs) {
+  return sn_lds_dec(nused, nslots, naggs).total;
+}
+/* largest dense slot count the decimal grouped kernel admits (160 KiB LDS) */
+static inline int sn_dec_max_slots(int nused, int naggs) {
+  const unsigned long long fixed = sn_dec_lds_bytes(nused, 0, naggs);
+  if (fixed >= SN_LDS_LIMIT) return 0;
+  return (int)((SN_LDS_LIMIT - fixed) /
+               ((unsigned long long)sn_dec_row_cells(naggs) * 8));
+}
+/* replication factor of the grouped LDS accumulator (lane l updates copy
+ * l % copies, so few-group shapes do not serialize a whole wave on one LDS
+ * address): the largest power of two <= 16 that keeps a block within half
+ * the CU's LDS (two resident blocks), or within all of it when one copy
+ * already needs more than half. */
+static inline int sn_dec_copies(int nused, int nslots, int naggs) {
+  const unsigned long long budget =
+      sn_dec_lds_bytes(nused, nslots, naggs) <= SN_LDS_LIMIT / 2
+          ? SN_LDS_LIMIT / 2 : SN_LDS_LIMIT;
+  int c = 1;
+  while (c < 16 && sn_dec_lds_bytes(nused, nslots * c * 2, naggs) <= budget)
+    c *= 2;
+  return c;
+}
+
+/* ---- launch geometry ---- */
+
+/* every block gets the same tile count (a ragged grid-stride leaves half the
+ * blocks with 2x work and CUs idle in the tail) */
+static inline int sn_balanced_grid(int ntiles, int cap) {
+  if (ntiles <= cap) return ntiles;
+  const int rounds = (ntiles + cap - 1) / cap;
+  return (ntiles + rounds - 1) / rounds;
+}
+
+/* one dense (keyless or direct-slot grouped) launch, as sn_launch_scan_agg
+ * performs it and as the engine sizes scratch and folds partials for it */
+enum {
+  SN_ROUTE_KEYLESS,   /* k_keyless */
+  SN_ROUTE_GLOBAL,    /* k_grouped_global: unbounded cardinality, or a pac
+                         accumulator too wide for LDS */
+  SN_ROUTE_LDS,       /* k_grouped_lds: > 16 slots, or per-agg counts */
+  SN_ROUTE_REG,       /* k_grouped_reg: Q1's shape */
+  SN_ROUTE_GROUPED    /* k_grouped */
+};
+typedef struct {
+  int route;
+  int grid;           /* blocks of the interpreted kernel */
+  int grid_compiled;  /* blocks of the query-compiled twin */
+  int global_acc;     /* accumulates into 8 XCD-private global copies (the
+                         caller zeroes them) instead of per-block rows */
+  int na_t, na1;      /* template aggregate count; accumulator row width */
+  int nv;             /* doubles per partial row */
+  int naggs1;         /* k_reduce row width (0: keyless layout) */
+  int out_stride;
+  unsigned long long lds;
+} sn_dense_launch;
+
+/* partial rows k_reduce folds == rows the scratch buffer must hold */
+static inline int sn_dense_rows(const sn_dense_launch *d, int compiled) {
+  return d->global_acc ? 8 : compiled ? d->grid_compiled : d->grid;
+}
+
+static inline sn_dense_launch sn_dense_launch_of(const sn_dev_plan *p,
+                                                 int ntiles) {
+  sn_dense_launch d;
+  const int ns = p->nslots, na = p->naggs, nused = p->nused;
+  d.na_t = sn_na_t(na);
+  d.na1 = p->pac ? 2 * na + 1 : na + 1;
+  d.out_stride = 2 * d.na_t + 1;
+  d.grid = ntiles <= 0 ? 1 : sn_balanced_grid(ntiles, SN_GRID_CAP);
+  /* > 16-slot partial rows are wide: the grid cap keeps scratch small */
+  d.grid_compiled = ns > 16 && d.grid > SN_GRID_BIGSLOT ? SN_GRID_BIGSLOT
+                                                        : d.grid;
+  d.global_acc = 0;
+  if (ns <= 1 && !p->pac) {
+    d.route = SN_ROUTE_KEYLESS;
+    d.nv = d.out_stride; d.naggs1 = 0;
+    d.lds = sn_lds_keyless(nused).total;
+    return d;
+  }
+  /* grouped layout (also keyless MIN/MAX plans routed through the grouped
+   * kernels with one slot) */
+  d.nv = (ns < 1 ? 1 : ns) * d.na1; d.naggs1 = d.na1;
+  if (ns > SN_RESULT_PAGE ||
+      (p->pac && sn_grouped_needs_global(nused, ns, d.na1))) {
+    d.route = SN_ROUTE_GLOBAL;
+    d.global_acc = 1;
+    d.lds = sn_lds_grouped_global(nused).total;
+  } else if (ns > 16 || p->pac) {
+    d.route = SN_ROUTE_LDS;
+    if (d.grid > SN_GRID_BIGSLOT) d.grid = SN_GRID_BIGSLOT;
+    d.lds = sn_lds_grouped_lds(nused, ns, d.na1).total;
+  } else if (p->jmode != 1 && ns <= SN_REG_SLOTS && na <= 6) {
+    d.route = SN_ROUTE_REG;
+    d.lds = sn_lds_grouped_reg(nused, na).total;
+  } else {
+    d.route = SN_ROUTE_GROUPED;
+    d.lds = sn_lds_grouped(nused, sn_grouped_ns_t(ns), na).total;
+  }
+  return d;
+}
 
 #ifdef __cplusplus
 extern "C" {
@@ -323,7 +485,7 @@ int sn_launch_scan_agg(const sn_dev_plan *plan,
                        const sn_dev_batch *dev_batches,
                        const sn_dev_tile *dev_tiles, int32_t ntiles,
                        double *dev_out,
-                       double *dev_scratch,  /* >= min(ntiles,SN_GRID_CAP) x nv */
+                       double *dev_scratch,  /* >= sn_dense_rows x nv doubles */
                        void *stream);
 
 /* exact decimal scan+filter+aggregate: block partials into dev_scratch

@@ -745,6 +745,187 @@ __device__ __forceinline__ void probe_sweep(const sn_dev_plan *P,
   }
 }
 
+/* ================= shared scan front end =================
+ * Every scan kernel below is a row phase plugged into the same three pieces:
+ * the LDS carve-up (scan_lds over engine_internal.h's sn_lds layout, which
+ * the launchers size from), the tile/chunk driver (scan_tiles) and the
+ * row-phase helpers (dense_slot, acc_row, hash_find_or_insert). */
+
+/* copy a plan struct into its LDS mirror: row-phase field reads become
+ * broadcast ds_reads instead of SGPR-spilled kernarg loads.  The caller
+ * places the barrier. */
+template <typename T>
+__device__ __forceinline__ void lds_mirror(T *dst_, const T *src_g) {
+  const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)src_g;
+  unsigned *dst = (unsigned *)dst_;
+  for (unsigned i = threadIdx.x; i < sizeof(T) / 4; i += WG) dst[i] = src[i];
+}
+
+struct ScanLds {
+  double *sval;
+  uint64_t *svalid, *sdead, *salive;
+  int16_t *sslot;        /* valid only for layouts with a slot image */
+  sn_dev_plan *P;
+  char *plan2, *acc;
+};
+
+/* carve the block's dynamic LDS by layout L */
+__device__ __forceinline__ ScanLds scan_lds(char *smem, const sn_lds &L) {
+  ScanLds S;
+  S.sval = (double *)smem;
+  S.svalid = (uint64_t *)(smem + L.svalid);
+  S.sdead = (uint64_t *)(smem + L.sdead);
+  S.salive = (uint64_t *)(smem + L.salive);
+  S.sslot = (int16_t *)(smem + L.sslot);
+  S.P = (sn_dev_plan *)(smem + L.plan);
+  S.plan2 = smem + L.plan2;
+  S.acc = smem + L.acc;
+  return S;
+}
+/* ... and start the plan mirror copy */
+__device__ __forceinline__ ScanLds scan_lds(char *smem, const sn_lds &L,
+                                            const sn_dev_plan *plan_g) {
+  const ScanLds S = scan_lds(smem, L);
+  lds_mirror(S.P, plan_g);
+  return S;
+}
+
+/* the tile/chunk driver: grid-stride over tiles; per tile hoist the column
+ * descriptors and decide stageability; per chunk land the image in LDS
+ * (staged registers or convert_chunk), barrier, issue the NEXT full chunk's
+ * loads so they fly under the row phase, run row_phase(batch, base, rows,
+ * clean), barrier.  STAGED = 0 drops the register pipeline (every chunk
+ * through convert_chunk). */
+template <int NC, int STAGED, typename RowPhase>
+__device__ __forceinline__ void scan_tiles(
+    const sn_dev_batch *__restrict__ batches,
+    const sn_dev_tile *__restrict__ tiles, int ntiles, int nused,
+    const ScanLds &S, RowPhase &&row_phase) {
+  Stage<STAGED ? NC : 1> st;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int num_rows = b.num_rows;
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
+    const int clean = b.clean;
+    [[maybe_unused]] ColRegs cr[NC];
+    int pipe = 0, staged = 0;
+    if constexpr (STAGED) {
+      hoist_cols(b, nused, cr);
+      pipe = batch_stageable(clean, nused, cr);
+      if (pipe && tile.row_start + CHUNK <= tile_end) {
+        stage_load(cr, nused, tile.row_start, st);
+        staged = 1;
+      }
+    }
+    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
+      const int rows = min(CHUNK, tile_end - base);
+      if (STAGED && staged) {
+        if constexpr (STAGED) stage_write(cr, nused, st, S.sval);
+      } else {
+        convert_chunk(b, nused, base, rows, num_rows, S.sval, S.svalid, S.sdead);
+      }
+      __syncthreads();
+      /* prefetch the NEXT full chunk under this chunk's row phase */
+      const int nbase = base + CHUNK;
+      const int next_staged = pipe && nbase + CHUNK <= tile_end;
+      if constexpr (STAGED) {
+        if (next_staged) stage_load(cr, nused, nbase, st);
+      }
+      row_phase(b, base, rows, clean);
+      __syncthreads();
+      staged = next_staged;
+    }
+  }
+}
+/* a row phase: ROW_PHASE(captures) { ... }.  Capture scalars by value and
+ * only the kernel's register accumulators by reference where a kernel sits
+ * at its register ceiling. */
+#define ROW_PHASE(...) [__VA_ARGS__](const sn_dev_batch &b, int base, \
+                                     int rows, int clean)              \
+    __attribute__((always_inline))
+
+/* dense group slot of row r: ((v0 - gbase[0]) * gmul0) + (v1 - gbase[1]);
+ * T is the slot width the kernel's accumulator indexing uses */
+template <typename T>
+__device__ __forceinline__ T dense_slot(const sn_dev_plan *P,
+                                        const double *sval, int ngroup,
+                                        int gc0, int gc1, int r) {
+  T slot = 0;
+  if (ngroup >= 1)
+    slot = (T)(((long long)sval[(size_t)gc0 * CHUNK + r] - P->gbase[0]) *
+               P->gmul0);
+  if (ngroup >= 2)
+    slot += (T)((long long)sval[(size_t)gc1 * CHUNK + r] - P->gbase[1]);
+  return slot;
+}
+/* composite GROUP BY dim_attr, fact_col: the probed attr gid widened by the
+ * dense fact-slot space */
+template <typename T>
+__device__ __forceinline__ T join_slot(const sn_dev_plan *P, const double *sval,
+                                       int pay, int gc0, int r) {
+  return (T)pay * P->jslot_mul +
+         (T)((long long)sval[(size_t)gc0 * CHUNK + r] - P->gbase[0]);
+}
+/* slot of a live row in the kernels that derive it per row: from the join
+ * payload image (jslot), alone or composite, else from the key columns */
+template <typename T>
+__device__ __forceinline__ T row_slot(const sn_dev_plan *P, const ScanLds &S,
+                                      int jslot, int ngroup, int gc0, int gc1,
+                                      int r) {
+  if (!jslot) return dense_slot<T>(P, S.sval, ngroup, gc0, gc1, r);
+  const int pay = S.sslot[r];
+  return ngroup >= 1 ? join_slot<T>(P, S.sval, pay, gc0, r) : (T)pay;
+}
+
+/* accumulate live row r into its accumulator row (LDS or global):
+ * [aggregates naggs][per-agg counts naggs, pac only][rowcount] */
+template <typename PTR>
+__device__ __forceinline__ void acc_row(PTR *row_acc, const sn_dev_plan *P,
+                                        int naggs, int na1, int pac, int clean,
+                                        const double *sval,
+                                        const uint64_t *svalid, int r) {
+  for (int a = 0; a < naggs; a++) {
+    const sn_dev_agg &A = P->aggs[a];
+    if (pac) {
+      const int av = clean ? 1 : agg_valid(A, svalid, r);
+      if (!av) continue;
+      (void)atomicAdd((double *)&row_acc[naggs + a], 1.0);
+    }
+    acc_cell(&row_acc[a], A.op, eval_agg(P, A, sval, r));
+  }
+  (void)atomicAdd((double *)&row_acc[na1 - 1], 1.0);
+}
+
+/* open-address find-or-insert of `key` (never SN_HASH_EMPTY) in a table of
+ * mask + 1 keys (global table, global segment or LDS); returns its index, or
+ * -1 when the table is full.  `fill`, when given, counts the inserts so the
+ * host can grow the table BEFORE load factor makes linear probing
+ * pathological. */
+template <typename KEYS>
+__device__ __forceinline__ int hash_find_or_insert(KEYS keys, unsigned mask,
+                                                   long long key,
+                                                   GAS int32_t *fill) {
+  unsigned h = (unsigned)mix64((unsigned long long)key) & mask;
+  for (unsigned it = 0; it <= mask; ++it) {
+    const long long k0 = keys[h];
+    if (k0 == key) return (int)h;
+    if (k0 == SN_HASH_EMPTY) {
+      const long long old = (long long)atomicCAS(
+          (unsigned long long *)&keys[h], (unsigned long long)SN_HASH_EMPTY,
+          (unsigned long long)key);
+      if (old == SN_HASH_EMPTY) {
+        if (fill) (void)atomicAdd((int *)fill, 1);
+        return (int)h;
+      }
+      if (old == key) return (int)h;
+      /* lost the insert race to a DIFFERENT key: step on */
+    }
+    h = (h + 1) & mask;
+  }
+  return -1;
+}
+
 /* ================= keyless kernel ================= */
 template <int NAGGS, int NC>
 __launch_bounds__(WG, NAGGS <= 4 ? 4 : 2)
@@ -756,141 +937,109 @@ __global__ void k_keyless(sn_dev_plan plan,
   const int tid = threadIdx.x;
   const int nused = plan.nused;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
-  /* plan mirrored into LDS: row-phase field reads become broadcast ds_reads
-   * instead of SGPR-spilled kernarg loads */
-  sn_dev_plan *P = (sn_dev_plan *)(salive + CHUNK / 64 + 2);
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
+  const ScanLds S = scan_lds(smem, sn_lds_keyless(nused), plan_g);
+  const sn_dev_plan *P = S.P;
+  double *const sval = S.sval;
+  uint64_t *const svalid = S.svalid, *const salive = S.salive;
 
   double sums[NAGGS], cnts[NAGGS], rcnt = 0.0;
 #pragma unroll
   for (int a = 0; a < NAGGS; a++) { sums[a] = 0.0; cnts[a] = 0.0; }
   const int naggs = plan.naggs;
   const int npd = plan.npreds_d, npi = plan.npreds_i;
-  constexpr int STAGED = 1;
 
-  Stage<STAGED ? NC : 1> st;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-    ColRegs cr[NC];
-    hoist_cols(b, nused, cr);
-    const int pipe = STAGED && batch_stageable(clean, nused, cr);
-
-    int staged = 0;
-    if (pipe && tile.row_start + CHUNK <= tile_end) {
-      stage_load(cr, nused, tile.row_start, st);
-      staged = 1;
-    }
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      if (staged) stage_write(cr, nused, st, sval);
-      else convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      /* prefetch the NEXT full chunk under this chunk's row phase */
-      const int nbase = base + CHUNK;
-      const int next_staged = pipe && nbase + CHUNK <= tile_end;
-      if (next_staged) stage_load(cr, nused, nbase, st);
-
-      /* fully-fused single pass (clean chunks, <=3 double preds, no join):
-       * one traversal computes predicates, aggregates and counts — the
-       * minimal LDS-read structure (matches the membw probe's shape) */
-      if (clean && npd <= 3 && npi == 0 && !plan.jkeys &&
-          plan.npreds_in == 0) {
-        double lo0 = -1e308, hi0 = 1e308, lo1 = lo0, hi1 = hi0, lo2 = lo0, hi2 = hi0;
-        int c0 = 0, c1 = 0, c2 = 0;
-        if (npd >= 1) { lo0 = P->preds_d[0].lo; hi0 = P->preds_d[0].hi; c0 = P->preds_d[0].cslot; }
-        if (npd >= 2) { lo1 = P->preds_d[1].lo; hi1 = P->preds_d[1].hi; c1 = P->preds_d[1].cslot; }
-        if (npd >= 3) { lo2 = P->preds_d[2].lo; hi2 = P->preds_d[2].hi; c2 = P->preds_d[2].cslot; }
-#pragma unroll 2
-        for (int k = 0; k < CHUNK / WG; k++) {
-          const int r = tid + k * WG;
-          const int inr = r < rows;
-          const double x0 = sval[(size_t)c0 * CHUNK + r];
-          const double x1 = sval[(size_t)c1 * CHUNK + r];
-          const double x2 = sval[(size_t)c2 * CHUNK + r];
-          const int ok = inr &&
-              (npd < 1 || (x0 >= lo0 && x0 <= hi0)) &&
-              (npd < 2 || (x1 >= lo1 && x1 <= hi1)) &&
-              (npd < 3 || (x2 >= lo2 && x2 <= hi2));
-          if (__popcll(__ballot(ok)) == 0) continue;
-#pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            if (a >= naggs) break;
-            const double va = eval_agg(P, P->aggs[a], sval, r);
-            sums[a] += ok ? va : 0.0;
-            cnts[a] += ok ? 1.0 : 0.0;
-          }
-          rcnt += ok ? 1.0 : 0.0;
-        }
-        __syncthreads();
-        staged = next_staged;
-        continue;
-      }
-
-      /* ---- row phase as sweep passes: each wave owns its 64-row words of
-       * the alive bitmap, so pred/agg passes need no barriers; plan params
-       * hoisted per pass (row-invariant LDS reads once, not per row) ---- */
-      alive_init(salive, sdead, rows, clean);
-      pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
-      if (plan.jkeys) probe_sweep(P, sval, salive, nullptr);
-#pragma unroll
-      for (int a = 0; a < NAGGS; a++) {
-        if (a >= naggs) break;
-        const sn_dev_agg A = P->aggs[a];
-#pragma unroll 2
-        for (int k = 0; k < CHUNK / WG; k++) {
-          const int r = tid + k * WG;
-          uint64_t w = salive[r >> 6];
-          if (!clean) {
-            if (A.nf >= 1) w &= svalid[(size_t)A.c0 * (CHUNK / 64) + (r >> 6)];
-            if (A.nf >= 2) w &= svalid[(size_t)A.c1 * (CHUNK / 64) + (r >> 6)];
-            if (A.nf >= 3) w &= svalid[(size_t)A.c2 * (CHUNK / 64) + (r >> 6)];
-          }
-          if (w == 0) continue;
-          const int m = (int)((w >> (tid & 63)) & 1ull);
-          const double val = eval_agg(P, A, sval, r);
-          sums[a] += m ? val : 0.0;
-          cnts[a] += m ? 1.0 : 0.0;
-        }
-      }
+  scan_tiles<NC, 1>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
+    /* fully-fused single pass (clean chunks, <=3 double preds, no join):
+     * one traversal computes predicates, aggregates and counts — the
+     * minimal LDS-read structure (matches the membw probe's shape) */
+    if (clean && npd <= 3 && npi == 0 && !plan.jkeys &&
+        plan.npreds_in == 0) {
+      double lo0 = -1e308, hi0 = 1e308, lo1 = lo0, hi1 = hi0, lo2 = lo0, hi2 = hi0;
+      int c0 = 0, c1 = 0, c2 = 0;
+      if (npd >= 1) { lo0 = P->preds_d[0].lo; hi0 = P->preds_d[0].hi; c0 = P->preds_d[0].cslot; }
+      if (npd >= 2) { lo1 = P->preds_d[1].lo; hi1 = P->preds_d[1].hi; c1 = P->preds_d[1].cslot; }
+      if (npd >= 3) { lo2 = P->preds_d[2].lo; hi2 = P->preds_d[2].hi; c2 = P->preds_d[2].cslot; }
 #pragma unroll 2
       for (int k = 0; k < CHUNK / WG; k++) {
         const int r = tid + k * WG;
-        rcnt += (double)((salive[r >> 6] >> (tid & 63)) & 1ull);
+        const int inr = r < rows;
+        const double x0 = sval[(size_t)c0 * CHUNK + r];
+        const double x1 = sval[(size_t)c1 * CHUNK + r];
+        const double x2 = sval[(size_t)c2 * CHUNK + r];
+        const int ok = inr &&
+            (npd < 1 || (x0 >= lo0 && x0 <= hi0)) &&
+            (npd < 2 || (x1 >= lo1 && x1 <= hi1)) &&
+            (npd < 3 || (x2 >= lo2 && x2 <= hi2));
+        if (__popcll(__ballot(ok)) == 0) continue;
+#pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          if (a >= naggs) break;
+          const double va = eval_agg(P, P->aggs[a], sval, r);
+          sums[a] += ok ? va : 0.0;
+          cnts[a] += ok ? 1.0 : 0.0;
+        }
+        rcnt += ok ? 1.0 : 0.0;
       }
-      __syncthreads();
-      staged = next_staged;
+      return;
     }
-  }
+
+    /* ---- row phase as sweep passes: each wave owns its 64-row words of
+     * the alive bitmap, so pred/agg passes need no barriers; plan params
+     * hoisted per pass (row-invariant LDS reads once, not per row) ---- */
+    alive_init(salive, S.sdead, rows, clean);
+    pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
+    if (plan.jkeys) probe_sweep(P, sval, salive, nullptr);
+#pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+      if (a >= naggs) break;
+      const sn_dev_agg A = P->aggs[a];
+#pragma unroll 2
+      for (int k = 0; k < CHUNK / WG; k++) {
+        const int r = tid + k * WG;
+        uint64_t w = salive[r >> 6];
+        if (!clean) {
+          if (A.nf >= 1) w &= svalid[(size_t)A.c0 * (CHUNK / 64) + (r >> 6)];
+          if (A.nf >= 2) w &= svalid[(size_t)A.c1 * (CHUNK / 64) + (r >> 6)];
+          if (A.nf >= 3) w &= svalid[(size_t)A.c2 * (CHUNK / 64) + (r >> 6)];
+        }
+        if (w == 0) continue;
+        const int m = (int)((w >> (tid & 63)) & 1ull);
+        const double val = eval_agg(P, A, sval, r);
+        sums[a] += m ? val : 0.0;
+        cnts[a] += m ? 1.0 : 0.0;
+      }
+    }
+#pragma unroll 2
+    for (int k = 0; k < CHUNK / WG; k++) {
+      const int r = tid + k * WG;
+      rcnt += (double)((salive[r >> 6] >> (tid & 63)) & 1ull);
+    }
+  });
 
   /* block partials to scratch (plain stores) — per-wave atomicAdd to the
    * same few global addresses serialized at ~45ns each (8K+ per address =
-   * a fixed ~0.35 ms per query); a tiny reduce kernel sums the partials */
-  double *bacc = (double *)(P + 1);
+   * a fixed ~0.35 ms per query); a tiny reduce kernel sums the partials.
+   * The row is [sums na_t][counts na_t][rowcount] with na_t the result
+   * stride's aggregate count, which the <12, *> instances serve at both
+   * 8 and 12. */
+  double *bacc = (double *)S.acc;
   {
-    const int NV = 2 * NAGGS + 1;
+    const int na_t = NAGGS <= 4 ? NAGGS : sn_na_t(naggs);
+    const int NV = 2 * na_t + 1;
     for (int i = tid; i < NV; i += WG) bacc[i] = 0.0;
     __syncthreads();
+    /* (no early exit on a >= na_t: a runtime trip count would leave the
+     * loop rolled and sums[] in scratch; those partials are zero anyway) */
 #pragma unroll
     for (int a = 0; a < NAGGS; a++) {
+      const int lead = (tid & 63) == 0 && a < na_t;
       double x = wave_sum(sums[a]);
-      if ((tid & 63) == 0 && x != 0.0) atomicAdd(bacc + a, x);
+      if (lead && x != 0.0) atomicAdd(bacc + a, x);
       x = wave_sum(cnts[a]);
-      if ((tid & 63) == 0 && x != 0.0) atomicAdd(bacc + NAGGS + a, x);
+      if (lead && x != 0.0) atomicAdd(bacc + na_t + a, x);
     }
     double x = wave_sum(rcnt);
-    if ((tid & 63) == 0 && x != 0.0) atomicAdd(bacc + 2 * NAGGS, x);
+    if ((tid & 63) == 0 && x != 0.0) atomicAdd(bacc + 2 * na_t, x);
     __syncthreads();
     for (int i = tid; i < NV; i += WG)
       out[(size_t)blockIdx.x * NV + i] = bacc[i];
@@ -910,60 +1059,27 @@ __global__ void k_grouped(sn_dev_plan plan,
                           const sn_dev_plan *__restrict__ plan_g,
                           const sn_dev_batch *__restrict__ batches,
                           const sn_dev_tile *__restrict__ tiles, int ntiles,
-                          double *__restrict__ out, int out_stride) {
+                          double *__restrict__ out) {
   const int tid = threadIdx.x;
-  const int wid = tid >> 6;
   const int nused = plan.nused;
   const int naggs = plan.naggs, ngroup = plan.ngroup;
   const int npd = plan.npreds_d, npi = plan.npreds_i;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
-  int16_t *sslot = (int16_t *)(salive + CHUNK / 64);
+  const ScanLds S = scan_lds(smem, sn_lds_grouped(nused, NSLOTS, naggs), plan_g);
+  const sn_dev_plan *P = S.P;
+  double *const sval = S.sval;
+  uint64_t *const svalid = S.svalid, *const salive = S.salive;
+  int16_t *const sslot = S.sslot;
   /* block accumulator: [NSLOTS][naggs+1], init once */
-  double *bacc = (double *)(sslot + CHUNK);
-  sn_dev_plan *P = (sn_dev_plan *)(bacc + NSLOTS * (naggs + 1) + 2);
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
-
+  double *bacc = (double *)S.acc;
   for (int i = tid; i < NSLOTS * (naggs + 1); i += WG) bacc[i] = 0.0;
   __syncthreads();
 
-  constexpr int STAGED = 1;
-  Stage<STAGED ? NC : 1> st;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-    ColRegs cr[NC];
-    hoist_cols(b, nused, cr);
-    const int pipe = STAGED && batch_stageable(clean, nused, cr);
-
-    int staged = 0;
-    if (pipe && tile.row_start + CHUNK <= tile_end) {
-      stage_load(cr, nused, tile.row_start, st);
-      staged = 1;
-    }
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      if (staged) stage_write(cr, nused, st, sval);
-      else convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      const int nbase = base + CHUNK;
-      const int next_staged = pipe && nbase + CHUNK <= tile_end;
-      if (next_staged) stage_load(cr, nused, nbase, st);
-
+  scan_tiles<NC, 1>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
       /* pass A: alive bitmap via sweeps + slot per row (wave-owned words,
        * no barrier needed before this block's own later passes) */
-      alive_init(salive, sdead, rows, clean);
+      alive_init(salive, S.sdead, rows, clean);
       pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
       if (plan.jkeys) {
         /* join: filter by probe; group-by-dim-attr takes its slot from the
@@ -975,26 +1091,17 @@ __global__ void k_grouped(sn_dev_plan plan,
 #pragma unroll
         for (int k = 0; k < CHUNK / WG; k++) {
           const int r = tid + k * WG;
-          int slot = 0;
-          if (ngroup >= 1)
-            slot = (int)(((long long)sval[(size_t)gc0 * CHUNK + r] -
-                          P->gbase[0]) * P->gmul0);
-          if (ngroup >= 2)
-            slot += (int)((long long)sval[(size_t)gc1 * CHUNK + r] -
-                          P->gbase[1]);
-          sslot[r] = (int16_t)slot;
+          sslot[r] = (int16_t)dense_slot<int>(P, sval, ngroup, gc0, gc1, r);
         }
       } else if (ngroup >= 1) {
         /* composite GROUP BY dim_attr, fact_col: probe_sweep staged the
-         * attr gid; widen it by the dense fact-slot space (dead rows keep
-         * garbage slots — they are never accumulated) */
+         * attr gid (dead rows keep garbage slots — they are never
+         * accumulated) */
         const int gc0 = plan.gcol[0];
 #pragma unroll
         for (int k = 0; k < CHUNK / WG; k++) {
           const int r = tid + k * WG;
-          const int slot = (int)sslot[r] * P->jslot_mul +
-              (int)((long long)sval[(size_t)gc0 * CHUNK + r] - P->gbase[0]);
-          sslot[r] = (int16_t)slot;
+          sslot[r] = (int16_t)join_slot<int>(P, sval, sslot[r], gc0, r);
         }
       }
 
@@ -1059,10 +1166,7 @@ __global__ void k_grouped(sn_dev_plan plan,
           }
         }
       }
-      __syncthreads();
-      staged = next_staged;
-    }
-  }
+  });
 
   /* flush block accumulator to a per-block scratch row (plain stores);
    * the reduce kernel folds rows into the final [slot][stride] layout.
@@ -1072,7 +1176,6 @@ __global__ void k_grouped(sn_dev_plan plan,
   const int NV = plan.nslots * (naggs + 1);
   for (int i = tid; i < NV; i += WG)
     out[(size_t)blockIdx.x * NV + i] = bacc[i];
-  (void)wid; (void)out_stride;
 }
 
 /* ---- LDS-accumulator grouped kernel (large slot counts: 17..1024) ----
@@ -1089,31 +1192,23 @@ void k_grouped_lds(sn_dev_plan plan,
                    const sn_dev_plan *__restrict__ plan_g,
                    const sn_dev_batch *__restrict__ batches,
                    const sn_dev_tile *__restrict__ tiles, int ntiles,
-                   double *__restrict__ out, int out_stride) {
+                   double *__restrict__ out) {
   const int tid = threadIdx.x;
   const int nused = plan.nused;
   const int naggs = plan.naggs, ngroup = plan.ngroup;
   const int npd = plan.npreds_d, npi = plan.npreds_i;
   const int nslots = plan.nslots;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
-  int16_t *sslot = (int16_t *)(salive + CHUNK / 64 + 2);   /* join-group */
-  sn_dev_plan *P = (sn_dev_plan *)((char *)sslot + CHUNK * 2);
-  double *bacc = (double *)(P + 1);   /* [nslots][naggs+1] */
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
-  /* pac: accumulator rows widen to [sums][per-agg counts][rowcount];
-   * min/max cells initialize to their ord-encoding identity (read ops from
-   * the by-value plan — the LDS mirror copy has no barrier yet) */
+  /* pac: accumulator rows widen to [sums][per-agg counts][rowcount] */
   const int pac = plan.pac;
   const int na1 = pac ? 2 * naggs + 1 : naggs + 1;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const ScanLds S =
+      scan_lds(smem, sn_lds_grouped_lds(nused, nslots, na1), plan_g);
+  const sn_dev_plan *P = S.P;
+  double *bacc = (double *)S.acc;   /* [nslots][na1] */
+  /* min/max cells initialize to their ord-encoding identity (read ops from
+   * the by-value plan — the LDS mirror copy has no barrier yet) */
   const int NV = nslots * na1;
   for (int i = tid; i < NV; i += WG) {
     const int a = i % na1;
@@ -1122,64 +1217,28 @@ void k_grouped_lds(sn_dev_plan plan,
   __syncthreads();
 
   const int gc0 = plan.gcol[0], gc1 = plan.gcol[1];
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      alive_init(salive, sdead, rows, clean);
-      pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
-      const int jslot = plan.jkeys && plan.jmode == 1;
-      if (plan.jkeys) probe_sweep(P, sval, salive, jslot ? sslot : nullptr);
+  const int jslot = plan.jkeys && plan.jmode == 1;
+  scan_tiles<1, 0>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
+    alive_init(S.salive, S.sdead, rows, clean);
+    pred_sweeps(P, npd, npi, clean, S.sval, S.svalid, S.salive);
+    if (plan.jkeys) probe_sweep(P, S.sval, S.salive, jslot ? S.sslot : nullptr);
 
 #pragma unroll 2
-      for (int k = 0; k < CHUNK / WG; k++) {
-        const int r = tid + k * WG;
-        const uint64_t w = salive[r >> 6];
-        if (w == 0) continue;
-        const int m = (int)((w >> (tid & 63)) & 1ull);
-        if (!m) continue;
-        int slot = 0;
-        if (jslot) {
-          slot = sslot[r];
-          if (ngroup >= 1)   /* composite dim_attr x fact_col */
-            slot = slot * P->jslot_mul +
-                   (int)((long long)sval[(size_t)gc0 * CHUNK + r] -
-                         P->gbase[0]);
-        } else {
-          if (ngroup >= 1)
-            slot = (int)(((long long)sval[(size_t)gc0 * CHUNK + r] -
-                          P->gbase[0]) * P->gmul0);
-          if (ngroup >= 2)
-            slot += (int)((long long)sval[(size_t)gc1 * CHUNK + r] -
-                          P->gbase[1]);
-        }
-        double *row_acc = bacc + (size_t)slot * na1;
-        for (int a = 0; a < naggs; a++) {
-          const sn_dev_agg &A = P->aggs[a];
-          if (pac) {
-            const int av = clean ? 1 : agg_valid(A, svalid, r);
-            if (!av) continue;
-            atomicAdd(&row_acc[naggs + a], 1.0);
-          }
-          acc_cell(&row_acc[a], A.op, eval_agg(P, A, sval, r));
-        }
-        atomicAdd(&row_acc[na1 - 1], 1.0);
-      }
-      __syncthreads();
+    for (int k = 0; k < CHUNK / WG; k++) {
+      const int r = tid + k * WG;
+      const uint64_t w = S.salive[r >> 6];
+      if (w == 0) continue;
+      const int m = (int)((w >> (tid & 63)) & 1ull);
+      if (!m) continue;
+      const int slot = row_slot<int>(P, S, jslot, ngroup, gc0, gc1, r);
+      acc_row(bacc + (size_t)slot * na1, P, naggs, na1, pac, clean, S.sval,
+              S.svalid, r);
     }
-  }
+  });
 
   __syncthreads();
   for (int i = tid; i < NV; i += WG)
     out[(size_t)blockIdx.x * NV + i] = bacc[i];
-  (void)out_stride;
 }
 
 /* ---- register-accumulator grouped kernel (small shapes: NSLOTS x NA
@@ -1196,24 +1255,18 @@ __global__ void k_grouped_reg(sn_dev_plan plan,
                               const sn_dev_plan *__restrict__ plan_g,
                               const sn_dev_batch *__restrict__ batches,
                               const sn_dev_tile *__restrict__ tiles, int ntiles,
-                              double *__restrict__ out, int out_stride) {
+                              double *__restrict__ out) {
   const int tid = threadIdx.x;
   const int nused = plan.nused;
   const int naggs = plan.naggs, ngroup = plan.ngroup;
   const int npd = plan.npreds_d, npi = plan.npreds_i;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
-  sn_dev_plan *P = (sn_dev_plan *)(salive + CHUNK / 64 + 2);
-  double *bacc = (double *)(P + 1);
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
+  const ScanLds S = scan_lds(smem, sn_lds_grouped_reg(nused, naggs), plan_g);
+  const sn_dev_plan *P = S.P;
+  double *const sval = S.sval;
+  uint64_t *const svalid = S.svalid, *const salive = S.salive;
+  double *bacc = (double *)S.acc;
   __syncthreads();
 
   const int gc0 = plan.gcol[0], gc1 = plan.gcol[1];
@@ -1227,35 +1280,11 @@ __global__ void k_grouped_reg(sn_dev_plan plan,
     for (int a = 0; a < NA; a++) sums[s][a] = 0.0;
   }
 
-  Stage<STAGED ? NC : 1> st;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-    ColRegs cr[NC];
-    hoist_cols(b, nused, cr);
-    const int pipe = STAGED && batch_stageable(clean, nused, cr);
-
-    int staged = 0;
-    if (STAGED && pipe && tile.row_start + CHUNK <= tile_end) {
-      if constexpr (STAGED) stage_load(cr, nused, tile.row_start, st);
-      staged = 1;
-    }
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      if (STAGED && staged) { if constexpr (STAGED) stage_write(cr, nused, st, sval); }
-      else convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      const int nbase = base + CHUNK;
-      const int next_staged = pipe && nbase + CHUNK <= tile_end;
-      if (STAGED && next_staged) { if constexpr (STAGED) stage_load(cr, nused, nbase, st); }
-
+  scan_tiles<NC, STAGED>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
       const int inline_preds = clean && npi == 0 && !plan.jkeys &&
                                plan.npreds_in == 0;
       if (!inline_preds) {
-        alive_init(salive, sdead, rows, clean);
+        alive_init(salive, S.sdead, rows, clean);
         pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
         if (plan.jkeys) probe_sweep(P, sval, salive, nullptr);
       }
@@ -1276,13 +1305,7 @@ __global__ void k_grouped_reg(sn_dev_plan plan,
           if (w == 0) continue;
           m = (int)((w >> (tid & 63)) & 1ull);
         }
-        int slot = 0;
-        if (ngroup >= 1)
-          slot = (int)(((long long)sval[(size_t)gc0 * CHUNK + r] -
-                        P->gbase[0]) * P->gmul0);
-        if (ngroup >= 2)
-          slot += (int)((long long)sval[(size_t)gc1 * CHUNK + r] -
-                        P->gbase[1]);
+        const int slot = dense_slot<int>(P, sval, ngroup, gc0, gc1, r);
         double va[NA];
 #pragma unroll
         for (int a = 0; a < NA; a++) {
@@ -1298,10 +1321,7 @@ __global__ void k_grouped_reg(sn_dev_plan plan,
             sums[s][a] = __builtin_fma(md, va[a], sums[s][a]);
         }
       }
-      __syncthreads();
-      staged = next_staged;
-    }
-  }
+  });
 
   /* final block reduction into a scratch row (like the keyless kernel) */
   const int NV = plan.nslots * (naggs + 1);
@@ -1321,7 +1341,6 @@ __global__ void k_grouped_reg(sn_dev_plan plan,
   __syncthreads();
   for (int i = tid; i < NV; i += WG)
     out[(size_t)blockIdx.x * NV + i] = bacc[i];
-  (void)out_stride;
 }
 
 /* ---- unbounded-cardinality grouped scan (the SHAMap-overflow analogue):
@@ -1341,17 +1360,8 @@ void k_grouped_global(sn_dev_plan plan,
   const int npd = plan.npreds_d, npi = plan.npreds_i;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
-  int16_t *sslot = (int16_t *)(salive + CHUNK / 64 + 2);
-  sn_dev_plan *P = (sn_dev_plan *)((char *)sslot + CHUNK * 2);
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
+  const ScanLds S = scan_lds(smem, sn_lds_grouped_global(nused), plan_g);
+  const sn_dev_plan *P = S.P;
   __syncthreads();
 
   /* 8-way XCD privatization (see the JIT twin): fold happens in k_reduce */
@@ -1360,57 +1370,25 @@ void k_grouped_global(sn_dev_plan plan,
   GAS double *acc = (GAS double *)(uintptr_t)gacc +
                     (size_t)(blockIdx.x & 7) * (size_t)plan.nslots * na1;
   const int gc0 = plan.gcol[0], gc1 = plan.gcol[1];
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      alive_init(salive, sdead, rows, clean);
-      pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
-      const int jslot = plan.jkeys && plan.jmode == 1;
-      if (plan.jkeys) probe_sweep(P, sval, salive, jslot ? sslot : nullptr);
+  const int jslot = plan.jkeys && plan.jmode == 1;
+  scan_tiles<1, 0>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
+    alive_init(S.salive, S.sdead, rows, clean);
+    pred_sweeps(P, npd, npi, clean, S.sval, S.svalid, S.salive);
+    if (plan.jkeys) probe_sweep(P, S.sval, S.salive, jslot ? S.sslot : nullptr);
 
 #pragma unroll 2
-      for (int k = 0; k < CHUNK / WG; k++) {
-        const int r = tid + k * WG;
-        const uint64_t w = salive[r >> 6];
-        if (w == 0) continue;
-        const int m = (int)((w >> (tid & 63)) & 1ull);
-        if (!m) continue;
-        long long slot = 0;
-        if (jslot) {
-          slot = sslot[r];
-          if (ngroup >= 1)   /* composite dim_attr x fact_col */
-            slot = slot * P->jslot_mul +
-                   ((long long)sval[(size_t)gc0 * CHUNK + r] - P->gbase[0]);
-        } else {
-          if (ngroup >= 1)
-            slot = ((long long)sval[(size_t)gc0 * CHUNK + r] -
-                    P->gbase[0]) * P->gmul0;
-          if (ngroup >= 2)
-            slot += (long long)sval[(size_t)gc1 * CHUNK + r] - P->gbase[1];
-        }
-        GAS double *row_acc = acc + (size_t)slot * na1;
-        for (int a = 0; a < naggs; a++) {
-          const sn_dev_agg &A = P->aggs[a];
-          if (pac) {
-            const int av = clean ? 1 : agg_valid(A, svalid, r);
-            if (!av) continue;
-            (void)atomicAdd((double *)&row_acc[naggs + a], 1.0);
-          }
-          acc_cell(&row_acc[a], A.op, eval_agg(P, A, sval, r));
-        }
-        (void)atomicAdd((double *)&row_acc[na1 - 1], 1.0);
-      }
-      __syncthreads();
+    for (int k = 0; k < CHUNK / WG; k++) {
+      const int r = tid + k * WG;
+      const uint64_t w = S.salive[r >> 6];
+      if (w == 0) continue;
+      const int m = (int)((w >> (tid & 63)) & 1ull);
+      if (!m) continue;
+      const long long slot =
+          row_slot<long long>(P, S, jslot, ngroup, gc0, gc1, r);
+      acc_row(acc + (size_t)slot * na1, P, naggs, na1, pac, clean, S.sval,
+              S.svalid, r);
     }
-  }
+  });
 }
 
 /* ---- sparse-key open-address hash aggregate ----
@@ -1438,34 +1416,6 @@ __device__ __forceinline__ long long sparse_key(const sn_dev_plan *P,
   return (long long)(((unsigned long long)k0 << 32) | k1);
 }
 
-__device__ __forceinline__ int hash_probe(long long key, long long *hk_,
-                                          int cap_log2, int32_t *ovf) {
-  GAS long long *hk = (GAS long long *)(uintptr_t)hk_;
-  if (key == SN_HASH_EMPTY) return 1 << cap_log2;   /* reserved row */
-  const unsigned mask = (1u << cap_log2) - 1;
-  unsigned h = (unsigned)mix64((unsigned long long)key) & mask;
-  for (unsigned it = 0; it <= mask; ++it) {
-    const long long k0 = hk[h];
-    if (k0 == key) return (int)h;
-    if (k0 == SN_HASH_EMPTY) {
-      const long long old = (long long)atomicCAS(
-          (unsigned long long *)&hk[h], (unsigned long long)SN_HASH_EMPTY,
-          (unsigned long long)key);
-      if (old == SN_HASH_EMPTY) {
-        /* we inserted: count the fill so the host can grow the table
-         * BEFORE load factor makes linear probing pathological */
-        (void)atomicAdd((int *)(uintptr_t)(ovf + 2), 1);
-        return (int)h;
-      }
-      if (old == key) return (int)h;
-      /* lost the insert race to a DIFFERENT key: step on */
-    }
-    h = (h + 1) & mask;
-  }
-  atomicOr((int *)(uintptr_t)ovf, 1);               /* table full */
-  return -1;
-}
-
 __global__ __launch_bounds__(WG, 1)
 void k_grouped_hash(sn_dev_plan plan,
                     const sn_dev_plan *__restrict__ plan_g,
@@ -1477,72 +1427,52 @@ void k_grouped_hash(sn_dev_plan plan,
   const int npd = plan.npreds_d, npi = plan.npreds_i;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
-  sn_dev_plan *P = (sn_dev_plan *)(salive + CHUNK / 64 + 2);
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
+  const ScanLds S = scan_lds(smem, sn_lds_hash(nused), plan_g);
+  const sn_dev_plan *P = S.P;
   __syncthreads();
 
   const int pac = plan.pac;
   const int na1 = pac ? 2 * naggs + 1 : naggs + 1;
   GAS double *acc = (GAS double *)(uintptr_t)plan.hacc;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      alive_init(salive, sdead, rows, clean);
-      pred_sweeps(P, npd, npi, clean, sval, svalid, salive);
-      if (plan.jkeys) probe_sweep(P, sval, salive, nullptr);
+  GAS long long *hk = (GAS long long *)(uintptr_t)plan.hkeys;
+  GAS int32_t *flags = (GAS int32_t *)(uintptr_t)plan.hflags;
+  const int cap = 1 << plan.hcap_log2;
+  scan_tiles<1, 0>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
+    alive_init(S.salive, S.sdead, rows, clean);
+    pred_sweeps(P, npd, npi, clean, S.sval, S.svalid, S.salive);
+    if (plan.jkeys) probe_sweep(P, S.sval, S.salive, nullptr);
 
 #pragma unroll 2
-      for (int k = 0; k < CHUNK / WG; k++) {
-        const int r = tid + k * WG;
-        const uint64_t w = salive[r >> 6];
-        if (w == 0) continue;
-        const int m = (int)((w >> (tid & 63)) & 1ull);
-        if (!m) continue;
-        /* a NULL key routes to the dedicated null-group row at cap+1
-         * (nullable keys are single-column by the engine contract) */
-        int kvalid = 1;
-        if (!clean)
-          kvalid = (int)((svalid[(size_t)plan.gcol[0] * (CHUNK / 64) +
+    for (int k = 0; k < CHUNK / WG; k++) {
+      const int r = tid + k * WG;
+      const uint64_t w = S.salive[r >> 6];
+      if (w == 0) continue;
+      const int m = (int)((w >> (tid & 63)) & 1ull);
+      if (!m) continue;
+      /* a NULL key routes to the dedicated null-group row at cap+1
+       * (nullable keys are single-column by the engine contract) */
+      int kvalid = 1;
+      if (!clean)
+        kvalid = (int)((S.svalid[(size_t)plan.gcol[0] * (CHUNK / 64) +
                                  (r >> 6)] >> (r & 63)) & 1ull);
-        int slot;
-        if (!kvalid) {
-          slot = (1 << plan.hcap_log2) + 1;
-        } else {
-          const long long key = sparse_key(P, sval, r);
-          slot = hash_probe(key, plan.hkeys, plan.hcap_log2, plan.hflags);
-          if (slot < 0) continue;                   /* overflow: host retries */
+      int slot;
+      if (!kvalid) {
+        slot = cap + 1;
+      } else {
+        const long long key = sparse_key(P, S.sval, r);
+        /* a REAL key of -1 lands in the reserved row at cap */
+        slot = key == SN_HASH_EMPTY
+                   ? cap
+                   : hash_find_or_insert(hk, (unsigned)cap - 1, key, flags + 2);
+        if (slot < 0) {                   /* table full: host grows, retries */
+          atomicOr((int *)flags, 1);
+          continue;
         }
-        GAS double *row_acc = acc + (size_t)slot * na1;
-        for (int a = 0; a < naggs; a++) {
-          const sn_dev_agg &A = P->aggs[a];
-          if (pac) {
-            const int av = clean ? 1 : agg_valid(A, svalid, r);
-            if (!av) continue;
-            (void)atomicAdd((double *)&row_acc[naggs + a], 1.0);
-          }
-          acc_cell(&row_acc[a], A.op, eval_agg(P, A, sval, r));
-        }
-        (void)atomicAdd((double *)&row_acc[na1 - 1], 1.0);
       }
-      __syncthreads();
+      acc_row(acc + (size_t)slot * na1, P, naggs, na1, pac, clean, S.sval,
+              S.svalid, r);
     }
-  }
+  });
 }
 
 /* ---- device-side join-table build (the partitioned-partitioned /
@@ -1561,7 +1491,6 @@ __global__ void k_fill_i64(long long *dst, long long n, long long v) {
  * [1] = table full */
 __global__ __launch_bounds__(WG, 2)
 void k_join_build(sn_dev_plan plan,
-                  const sn_dev_plan *__restrict__ plan_g,
                   const sn_dev_batch *__restrict__ batches,
                   const sn_dev_tile *__restrict__ tiles, int ntiles,
                   long long *__restrict__ hk_, int32_t *__restrict__ hp_,
@@ -1574,31 +1503,18 @@ void k_join_build(sn_dev_plan plan,
   const unsigned mask = (1u << cap_log2) - 1;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sval = (double *)smem;
-  uint64_t *svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  uint64_t *sdead = svalid + (size_t)nused * (CHUNK / 64);
-  uint64_t *salive = sdead + CHUNK / 64;
+  const ScanLds S = scan_lds(smem, sn_lds_join_build(nused));
+  double *const sval = S.sval;
+  uint64_t *const salive = S.salive;
 
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      convert_chunk(b, nused, base, rows, num_rows, sval, svalid, sdead);
-      __syncthreads();
-      alive_init(salive, sdead, rows, clean);
+  scan_tiles<1, 0>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
+      alive_init(salive, S.sdead, rows, clean);
       if (!clean) {
         /* null build keys never join (SQL equality) */
-        const int tid64 = tid & 63;
-        (void)tid64;
 #pragma unroll
         for (int k = 0; k < CHUNK / WG; k++) {
           const int r = tid + k * WG;
-          uint64_t w = svalid[(size_t)0 * (CHUNK / 64) + (r >> 6)];
+          uint64_t w = S.svalid[(size_t)0 * (CHUNK / 64) + (r >> 6)];
           if ((tid & 63) == 0) salive[r >> 6] &= w;
         }
       }
@@ -1646,9 +1562,7 @@ void k_join_build(sn_dev_plan plan,
         }
         if (!done) atomicOr((int *)&flags[1], 1);
       }
-      __syncthreads();
-    }
-  }
+  });
 }
 
 /* densify the open-address table into a payload LUT over [lmin, lmax] */
@@ -1681,19 +1595,12 @@ extern "C" int sn_launch_join_build(const sn_dev_plan *plan,
                        dim3(256), 0, s, (long long *)hp, cap / 2,
                        (long long)0x8000000080000000ull);
   }
-  int grid;
   if (ntiles <= 0) return (int)hipGetLastError();
-  if (ntiles <= SN_GRID_CAP) grid = ntiles;
-  else {
-    int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
-    grid = (ntiles + rounds - 1) / rounds;
-  }
-  size_t lds = (size_t)plan->nused * CHUNK * 8 +
-               (size_t)plan->nused * (CHUNK / 64) * 8 +
-               2 * (CHUNK / 64) * 8 + 64;
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
+  const size_t lds = sn_lds_join_build(plan->nused).total;
+  if (lds > SN_LDS_LIMIT) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_join_build, dim3(grid), dim3(WG), lds, s,
-                     *plan, dev_plan, dev_batches, dev_tiles, ntiles,
+                     *plan, dev_batches, dev_tiles, ntiles,
                      hk, hp, cap_log2, has_attr, flags);
   return (int)hipGetLastError();
 }
@@ -1740,17 +1647,10 @@ extern "C" int sn_launch_hash_scan(const sn_dev_plan *plan,
                                    const sn_dev_tile *dev_tiles, int32_t ntiles,
                                    void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  int grid;
   if (ntiles <= 0) return 0;
-  if (ntiles <= SN_GRID_CAP) grid = ntiles;
-  else {
-    int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
-    grid = (ntiles + rounds - 1) / rounds;
-  }
-  size_t lds = (size_t)plan->nused * CHUNK * 8 +
-               (size_t)plan->nused * (CHUNK / 64) * 8 +
-               2 * (CHUNK / 64) * 8 + sizeof(sn_dev_plan) + 64;
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
+  const size_t lds = sn_lds_hash(plan->nused).total;
+  if (lds > SN_LDS_LIMIT) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_grouped_hash, dim3(grid), dim3(WG), lds, s,
                      *plan, dev_plan, dev_batches, dev_tiles, ntiles);
   return (int)hipGetLastError();
@@ -1832,19 +1732,8 @@ void k_radix_agg_lds(const sn_dev_plan *__restrict__ plan_g,
       (void)atomicAdd((double *)&row[na1 - 1], 1.0);
       continue;
     }
-    unsigned h = (unsigned)mix64((unsigned long long)key) & smask;
-    int slot = -1;
-    for (unsigned it = 0; it <= smask; ++it) {
-      const long long k0 = skeys[h];
-      if (k0 == key) { slot = (int)h; break; }
-      if (k0 == SN_HASH_EMPTY) {
-        const long long old = (long long)atomicCAS(
-            (unsigned long long *)&skeys[h], (unsigned long long)SN_HASH_EMPTY,
-            (unsigned long long)key);
-        if (old == SN_HASH_EMPTY || old == key) { slot = (int)h; break; }
-      }
-      h = (h + 1) & smask;
-    }
+    /* (the compaction below counts the fill) */
+    const int slot = hash_find_or_insert(skeys, smask, key, nullptr);
     if (slot < 0) { atomicOr((int *)flags, 1); continue; }   /* table full */
     double *row = sacc + (size_t)slot * na1;
     for (int a = 0; a < naggs; a++) acc_cell(&row[a], ops[a], rec[1 + a]);
@@ -1919,25 +1808,9 @@ void k_radix_agg_glob(const sn_dev_plan *__restrict__ plan_g) {
     if (key == SN_HASH_EMPTY) {
       slot = cap;                                   /* reserved row */
     } else {
-      unsigned h = (unsigned)mix64((unsigned long long)key) & smask;
-      slot = -1;
-      for (unsigned it = 0; it <= smask; ++it) {
-        const int s = segbase + (int)h;
-        const long long k0 = hk[s];
-        if (k0 == key) { slot = s; break; }
-        if (k0 == SN_HASH_EMPTY) {
-          const long long old = (long long)atomicCAS(
-              (unsigned long long *)&hk[s], (unsigned long long)SN_HASH_EMPTY,
-              (unsigned long long)key);
-          if (old == SN_HASH_EMPTY) {
-            (void)atomicAdd((int *)(flags + 2), 1);
-            slot = s; break;
-          }
-          if (old == key) { slot = s; break; }
-        }
-        h = (h + 1) & smask;
-      }
+      slot = hash_find_or_insert(hk + segbase, smask, key, flags + 2);
       if (slot < 0) { atomicOr((int *)flags, 1); continue; }  /* segment full */
+      slot += segbase;
     }
     GAS double *row = acc + (size_t)slot * na1;
     for (int a = 0; a < naggs; a++) acc_cell(&row[a], ops[a], rec[1 + a]);
@@ -2298,88 +2171,47 @@ extern "C" int sn_launch_scan_agg(const sn_dev_plan *plan,
                                   double *dev_out, double *dev_scratch,
                                   void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  /* balance: every block gets the same tile count (a ragged grid-stride
-   * leaves half the blocks with 2x work and CUs idle in the tail) */
-  int grid;
-  if (ntiles <= 0) grid = 1;
-  else if (ntiles <= SN_GRID_CAP) grid = ntiles;
-  else {
-    int rounds = (ntiles + SN_GRID_CAP - 1) / SN_GRID_CAP;
-    grid = (ntiles + rounds - 1) / rounds;
-  }
-  const int ns = plan->nslots, na = plan->naggs;
-  const int na_t = na <= 2 ? 2 : na <= 4 ? 4 : na <= 8 ? 8 : 12;
-  size_t lds = (size_t)plan->nused * CHUNK * 8 +
-               (size_t)plan->nused * (CHUNK / 64) * 8 +
-               2 * (CHUNK / 64) * 8 +            /* sdead + salive */
-               sizeof(sn_dev_plan) + 512;        /* plan mirror + keyless bacc */
-  hipError_t err;
+  const sn_dense_launch d = sn_dense_launch_of(plan, ntiles);
+  if (d.lds > SN_LDS_LIMIT) return (int)hipErrorInvalidValue;
+  const int grid = d.grid, ns = plan->nslots, na = plan->naggs;
+  const size_t lds = (size_t)d.lds;
   const bool nc4 = plan->nused <= 4;
-  const int na1 = plan->pac ? 2 * na + 1 : na + 1;
-  int nv, naggs1, out_stride;
-  if (ns <= 1 && !plan->pac) {
-    nv = 2 * na_t + 1; naggs1 = 0; out_stride = nv;
-  } else {
-    /* grouped layout (also keyless MIN/MAX plans routed through the
-     * grouped kernels with one slot) */
-    nv = (ns < 1 ? 1 : ns) * na1; naggs1 = na1; out_stride = 2 * na_t + 1;
-  }
-#define KL(A, NCv) hipLaunchKernelGGL((k_keyless<A, NCv>), dim3(grid), dim3(WG), lds, s, \
-        *plan, dev_plan, dev_batches, dev_tiles, ntiles, dev_scratch)
-#define KG(S, NCv) hipLaunchKernelGGL((k_grouped<S, NCv>), dim3(grid), dim3(WG), lds, s, \
-        *plan, dev_plan, dev_batches, dev_tiles, ntiles, dev_scratch, out_stride)
-  if (ns <= 1 && !plan->pac) {
-    if (na <= 2) { if (nc4) KL(2, 4); else KL(2, 8); }
-    else if (na <= 4) { if (nc4) KL(4, 4); else KL(4, 8); }
-    else { if (nc4) KL(12, 4); else KL(12, 8); }
-  } else if (ns > SN_RESULT_PAGE ||
-             (plan->pac &&
-              sn_grouped_needs_global(plan->nused, ns, na1))) {
-    /* unbounded cardinality (or a pac accumulator too wide for LDS):
-     * global f64 atomics into the (host-zeroed) scratch accumulator */
-    lds += (CHUNK / 64) * 8 + CHUNK * 2 + sizeof(sn_dev_plan) + 64;
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_grouped_global, dim3(grid), dim3(WG), lds, s,
-                       *plan, dev_plan, dev_batches, dev_tiles, ntiles,
-                       dev_scratch);
-    grid = 8;   /* k_reduce folds the 8 XCD-private copies */
-  } else if (ns > 16 || plan->pac) {
-    /* large-cardinality LDS hash-aggregate path (also the per-agg-count
-     * path for nullable aggregate inputs at any slot count): the LDS
-     * accumulator bounds the grid so scratch rows stay small */
-    if (grid > SN_GRID_BIGSLOT) grid = SN_GRID_BIGSLOT;
-    lds += (CHUNK / 64) * 8 + CHUNK * 2 + (size_t)ns * na1 * 8 + 64;
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_grouped_lds, dim3(grid), dim3(WG), lds, s,
-                       *plan, dev_plan, dev_batches, dev_tiles, ntiles,
-                       dev_scratch, out_stride);
-  } else if (plan->jmode != 1 && ns <= 8 && na <= 6) {
-    /* register-accumulator grouped kernel (Q1's shape) */
-    lds += (CHUNK / 64) * 8 + (size_t)8 * (na + 1) * 8 + 64;
-#define KGR(S, A, NCv) hipLaunchKernelGGL((k_grouped_reg<S, A, NCv>), dim3(grid), \
-        dim3(WG), lds, s, *plan, dev_plan, dev_batches, dev_tiles, ntiles, \
-        dev_scratch, out_stride)
-    /* (measured: an unstaged 3-waves/SIMD variant loses 20% — staging
-     * beats occupancy for the grouped shape as well) */
-    if (nc4) KGR(8, 6, 4); else KGR(8, 6, 8);
-#undef KGR
-  } else {
-    /* bacc + plan-mirror offsets inside the kernel use the TEMPLATE slot
-     * count — size the dynamic LDS with it, not the runtime ns */
-    const int ns_t = ns <= 4 ? 4 : ns <= 8 ? 8 : 16;
-    lds += (CHUNK / 64) * 8 + CHUNK * 2 + (size_t)ns_t * (na + 1) * 8 + 16;
-    if (ns <= 4) { if (nc4) KG(4, 4); else KG(4, 8); }
-    else if (ns <= 8) { if (nc4) KG(8, 4); else KG(8, 8); }
-    else if (ns <= 16) { if (nc4) KG(16, 4); else KG(16, 8); }
-    else return (int)hipErrorInvalidValue;
+#define SCAN(K) hipLaunchKernelGGL((K), dim3(grid), dim3(WG), lds, s, *plan, \
+        dev_plan, dev_batches, dev_tiles, ntiles, dev_scratch)
+#define KL(A, NCv) SCAN((k_keyless<A, NCv>))
+#define KG(S, NCv) SCAN((k_grouped<S, NCv>))
+  switch (d.route) {
+    case SN_ROUTE_KEYLESS:
+      if (na <= 2) { if (nc4) KL(2, 4); else KL(2, 8); }
+      else if (na <= 4) { if (nc4) KL(4, 4); else KL(4, 8); }
+      else { if (nc4) KL(12, 4); else KL(12, 8); }
+      break;
+    case SN_ROUTE_GLOBAL:
+      /* global f64 atomics into the (host-zeroed) scratch accumulator */
+      SCAN(k_grouped_global);
+      break;
+    case SN_ROUTE_LDS:
+      SCAN(k_grouped_lds);
+      break;
+    case SN_ROUTE_REG:
+      /* (measured: an unstaged 3-waves/SIMD variant loses 20% — staging
+       * beats occupancy for the grouped shape as well) */
+      if (nc4) SCAN((k_grouped_reg<SN_REG_SLOTS, 6, 4>));
+      else SCAN((k_grouped_reg<SN_REG_SLOTS, 6, 8>));
+      break;
+    default:
+      if (ns <= 4) { if (nc4) KG(4, 4); else KG(4, 8); }
+      else if (ns <= 8) { if (nc4) KG(8, 4); else KG(8, 8); }
+      else { if (nc4) KG(16, 4); else KG(16, 8); }
+      break;
   }
 #undef KL
 #undef KG
-  hipLaunchKernelGGL(k_reduce, dim3(nv), dim3(WG), 0, s,
-                     dev_scratch, grid, nv, dev_out, naggs1, out_stride,
-                     dev_plan);
-  err = hipGetLastError();
-  return (int)err;
+#undef SCAN
+  hipLaunchKernelGGL(k_reduce, dim3(d.nv), dim3(WG), 0, s,
+                     dev_scratch, sn_dense_rows(&d, 0), d.nv, dev_out,
+                     d.naggs1, d.out_stride, dev_plan);
+  return (int)hipGetLastError();
 }
 
 /* ================= exact DECIMAL aggregation =================
@@ -2475,37 +2307,24 @@ __device__ __forceinline__ u64_t dec_cell0_ident(int op) {
   return op == 1 ? ~0ull : 0ull;   /* MIN starts at the top, MAX/SUM at 0 */
 }
 
-/* LDS carve-up shared by both decimal kernels (sn_dec_lds_bytes) */
-struct DecSmem {
-  double *sval;
-  uint64_t *svalid, *sdead, *salive;
-  sn_dev_plan *P;
-  sn_dev_dec_plan *D;
-  u64_t *bacc;
-};
-__device__ __forceinline__ DecSmem dec_smem(char *smem, int nused,
-                                            const sn_dev_plan *plan_g,
-                                            const sn_dev_dec_plan *dec_g) {
-  DecSmem s;
-  s.sval = (double *)smem;
-  s.svalid = (uint64_t *)(smem + (size_t)nused * CHUNK * 8);
-  s.sdead = s.svalid + (size_t)nused * (CHUNK / 64);
-  s.salive = s.sdead + CHUNK / 64;
-  s.P = (sn_dev_plan *)(s.salive + CHUNK / 64 + 2);
-  s.D = (sn_dev_dec_plan *)(s.P + 1);
-  s.bacc = (u64_t *)(s.D + 1);
-  const int tid = threadIdx.x;
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)plan_g;
-    unsigned *dst = (unsigned *)s.P;
-    for (unsigned i = tid; i < sizeof(sn_dev_plan) / 4; i += WG) dst[i] = src[i];
-  }
-  {
-    const GAS unsigned *src = (const GAS unsigned *)(uintptr_t)dec_g;
-    unsigned *dst = (unsigned *)s.D;
-    for (unsigned i = tid; i < sizeof(sn_dev_dec_plan) / 4; i += WG) dst[i] = src[i];
-  }
-  return s;
+/* combine accumulator (y2:y1:y0) into (x2:x1:x0): 192-bit sum with carry,
+ * or min / max of the sign-biased cell 0 */
+__device__ __forceinline__ void dec_fold(int op, u64_t &x0, u64_t &x1,
+                                         u64_t &x2, u64_t y0, u64_t y1,
+                                         u64_t y2) {
+  if (op == 0) acc192_add(x0, x1, x2, y0, y1, y2);
+  else if (op == 1) x0 = y0 < x0 ? y0 : x0;
+  else x0 = y0 > x0 ? y0 : x0;
+}
+
+/* the decimal kernels' LDS: the shared layout with both plan mirrors */
+__device__ __forceinline__ ScanLds dec_lds(char *smem, int nused,
+                                           const sn_dev_plan *plan_g,
+                                           const sn_dev_dec_plan *dec_g) {
+  /* (the accumulator size does not move any offset) */
+  const ScanLds S = scan_lds(smem, sn_lds_dec(nused, 0, 0), plan_g);
+  lds_mirror((sn_dev_dec_plan *)S.plan2, dec_g);
+  return S;
 }
 
 /* ---- keyless: per-lane register accumulators, reduced across the wave
@@ -2524,49 +2343,29 @@ void k_dec_keyless(sn_dev_plan plan,
   const int nused = plan.nused;
   const int npd = plan.npreds_d, npi = plan.npreds_i;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const DecSmem S = dec_smem(smem, nused, plan_g, dec_g);
+  const ScanLds S = dec_lds(smem, nused, plan_g, dec_g);
+  const sn_dev_dec_plan *D = (const sn_dev_dec_plan *)S.plan2;
   __syncthreads();
-  const int naggs = S.D->naggs;
+  const int naggs = D->naggs;
 
   u64_t l0[NA], l1[NA], l2[NA];
   unsigned cnt[NA], ovf[NA];
   unsigned rcnt = 0;
 #pragma unroll
   for (int a = 0; a < NA; a++) {
-    l0[a] = a < naggs ? dec_cell0_ident(S.D->aggs[a].op) : 0ull;
+    l0[a] = a < naggs ? dec_cell0_ident(D->aggs[a].op) : 0ull;
     l1[a] = 0; l2[a] = 0; cnt[a] = 0; ovf[a] = 0;
   }
 
-  Stage<NC> st;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-    ColRegs cr[NC];
-    hoist_cols(b, nused, cr);
-    const int pipe = batch_stageable(clean, nused, cr);
-    int staged = 0;
-    if (pipe && tile.row_start + CHUNK <= tile_end) {
-      stage_load(cr, nused, tile.row_start, st);
-      staged = 1;
-    }
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      if (staged) stage_write(cr, nused, st, S.sval);
-      else convert_chunk(b, nused, base, rows, num_rows, S.sval, S.svalid, S.sdead);
-      __syncthreads();
-      /* prefetch the NEXT full chunk under this chunk's row phase */
-      const int nbase = base + CHUNK;
-      const int next_staged = pipe && nbase + CHUNK <= tile_end;
-      if (next_staged) stage_load(cr, nused, nbase, st);
+  /* (by-value captures: <12, 4> sits at 255 VGPRs with two waves per SIMD) */
+  scan_tiles<NC, 1>(batches, tiles, ntiles, nused, S,
+                    ROW_PHASE(=, &l0, &l1, &l2, &cnt, &ovf, &rcnt) {
       alive_init(S.salive, S.sdead, rows, clean);
       pred_sweeps(S.P, npd, npi, clean, S.sval, S.svalid, S.salive);
 #pragma unroll
       for (int a = 0; a < NA; a++) {
         if (a >= naggs) break;
-        const sn_dev_dec_agg A = S.D->aggs[a];
+        const sn_dev_dec_agg A = D->aggs[a];
 #pragma unroll 2
         for (int k = 0; k < CHUNK / WG; k++) {
           const int r = tid + k * WG;
@@ -2591,19 +2390,16 @@ void k_dec_keyless(sn_dev_plan plan,
         const int r = tid + k * WG;
         rcnt += (unsigned)((S.salive[r >> 6] >> (tid & 63)) & 1ull);
       }
-      __syncthreads();
-      staged = next_staged;
-    }
-  }
+  });
 
   /* wave reduction with carries, then the 4 wave partials fold in LDS */
   const int RC = SN_DEC_ROW_CELLS(naggs);
-  u64_t *wpart = S.bacc + RC;              /* [WG/64][RC] */
+  u64_t *wpart = (u64_t *)S.acc + RC;      /* [WG/64][RC] */
   const int wid = tid >> 6;
 #pragma unroll
   for (int a = 0; a < NA; a++) {
     if (a >= naggs) break;
-    const int op = S.D->aggs[a].op;
+    const int op = D->aggs[a].op;
     u64_t x0 = l0[a], x1 = l1[a], x2 = l2[a];
     u64_t c = cnt[a], o = ovf[a];
 #pragma unroll
@@ -2613,9 +2409,7 @@ void k_dec_keyless(sn_dev_plan plan,
       const u64_t y2 = __shfl_down(x2, off, 64);
       c += __shfl_down(c, off, 64);
       o += __shfl_down(o, off, 64);
-      if (op == 0) acc192_add(x0, x1, x2, y0, y1, y2);
-      else if (op == 1) x0 = y0 < x0 ? y0 : x0;
-      else x0 = y0 > x0 ? y0 : x0;
+      dec_fold(op, x0, x1, x2, y0, y1, y2);
     }
     if ((tid & 63) == 0) {
       u64_t *cell = wpart + (size_t)wid * RC + a * SN_DEC_CELLS;
@@ -2630,14 +2424,12 @@ void k_dec_keyless(sn_dev_plan plan,
   }
   __syncthreads();
   if (tid < naggs) {
-    const int op = S.D->aggs[tid].op;
+    const int op = D->aggs[tid].op;
     const u64_t *c0 = wpart + tid * SN_DEC_CELLS;
     u64_t x0 = c0[0], x1 = c0[1], x2 = c0[2], c = c0[3], o = c0[4];
     for (int w = 1; w < WG / 64; w++) {
       const u64_t *cw = c0 + (size_t)w * RC;
-      if (op == 0) acc192_add(x0, x1, x2, cw[0], cw[1], cw[2]);
-      else if (op == 1) x0 = cw[0] < x0 ? cw[0] : x0;
-      else x0 = cw[0] > x0 ? cw[0] : x0;
+      dec_fold(op, x0, x1, x2, cw[0], cw[1], cw[2]);
       c += cw[3]; o += cw[4];
     }
     u64_t *dst = out + (size_t)blockIdx.x * RC + tid * SN_DEC_CELLS;
@@ -2672,45 +2464,23 @@ void k_dec_grouped(sn_dev_plan plan,
   const int npd = plan.npreds_d, npi = plan.npreds_i;
   const int nslots = plan.nslots;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const DecSmem S = dec_smem(smem, nused, plan_g, dec_g);
+  const ScanLds S = dec_lds(smem, nused, plan_g, dec_g);
+  const sn_dev_dec_plan *D = (const sn_dev_dec_plan *)S.plan2;
   __syncthreads();
-  const int naggs = S.D->naggs;
+  const int naggs = D->naggs;
   const int RC = SN_DEC_ROW_CELLS(naggs);
   const int NV = nslots * RC;
-  u64_t *bacc = S.bacc;
+  u64_t *bacc = (u64_t *)S.acc;
   for (int i = tid; i < NV * copies; i += WG) {
     const int ci = i % RC;
     const int a = ci / SN_DEC_CELLS;
     bacc[i] = (ci < RC - 1 && ci % SN_DEC_CELLS == 0)
-                  ? dec_cell0_ident(S.D->aggs[a].op) : 0ull;
+                  ? dec_cell0_ident(D->aggs[a].op) : 0ull;
   }
   __syncthreads();
 
   const int gc0 = plan.gcol[0], gc1 = plan.gcol[1];
-  Stage<NC> st;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const sn_dev_tile tile = tiles[t];
-    const sn_dev_batch &b = batches[tile.batch];
-    const int num_rows = b.num_rows;
-    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
-    const int clean = b.clean;
-    ColRegs cr[NC];
-    hoist_cols(b, nused, cr);
-    const int pipe = batch_stageable(clean, nused, cr);
-    int staged = 0;
-    if (pipe && tile.row_start + CHUNK <= tile_end) {
-      stage_load(cr, nused, tile.row_start, st);
-      staged = 1;
-    }
-    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
-      const int rows = min(CHUNK, tile_end - base);
-      if (staged) stage_write(cr, nused, st, S.sval);
-      else convert_chunk(b, nused, base, rows, num_rows, S.sval, S.svalid, S.sdead);
-      __syncthreads();
-      /* prefetch the NEXT full chunk under this chunk's row phase */
-      const int nbase = base + CHUNK;
-      const int next_staged = pipe && nbase + CHUNK <= tile_end;
-      if (next_staged) stage_load(cr, nused, nbase, st);
+  scan_tiles<NC, 1>(batches, tiles, ntiles, nused, S, ROW_PHASE(&) {
       alive_init(S.salive, S.sdead, rows, clean);
       pred_sweeps(S.P, npd, npi, clean, S.sval, S.svalid, S.salive);
       /* slot per row first (-1: dead), then aggregate-outer sweeps so each
@@ -2722,13 +2492,7 @@ void k_dec_grouped(sn_dev_plan plan,
       for (int k = 0; k < CHUNK / WG; k++) {
         const int r = tid + k * WG;
         const int alive = (int)((S.salive[r >> 6] >> (tid & 63)) & 1ull);
-        int slot = 0;
-        if (ngroup >= 1)
-          slot = (int)(((long long)S.sval[(size_t)gc0 * CHUNK + r] -
-                        S.P->gbase[0]) * S.P->gmul0);
-        if (ngroup >= 2)
-          slot += (int)((long long)S.sval[(size_t)gc1 * CHUNK + r] -
-                        S.P->gbase[1]);
+        const int slot = dense_slot<int>(S.P, S.sval, ngroup, gc0, gc1, r);
         /* (a live row's slot is in range by construction; the bound keeps
          * a corrupt key from writing outside the accumulator) */
         slots[k] = (alive && (unsigned)slot < (unsigned)nslots) ? slot : -1;
@@ -2736,7 +2500,7 @@ void k_dec_grouped(sn_dev_plan plan,
           (void)atomicAdd(&mybase[(size_t)slots[k] * RC + RC - 1], 1ull);
       }
       for (int a = 0; a < naggs; a++) {
-        const sn_dev_dec_agg A = S.D->aggs[a];
+        const sn_dev_dec_agg A = D->aggs[a];
 #pragma unroll
         for (int k = 0; k < CHUNK / WG; k++) {
           if (slots[k] < 0) continue;
@@ -2772,10 +2536,7 @@ void k_dec_grouped(sn_dev_plan plan,
           }
         }
       }
-      __syncthreads();
-      staged = next_staged;
-    }
-  }
+  });
   __syncthreads();
   /* flush: one thread per (slot, aggregate | rowcount) folds the copies */
   for (int i = tid; i < nslots * (naggs + 1); i += WG) {
@@ -2788,14 +2549,12 @@ void k_dec_grouped(sn_dev_plan plan,
       dst[RC - 1] = rc;
       continue;
     }
-    const int op = S.D->aggs[a].op;
+    const int op = D->aggs[a].op;
     u64_t x0 = dec_cell0_ident(op), x1 = 0, x2 = 0, cn = 0, ov = 0;
     for (int c = 0; c < copies; c++) {
       const u64_t *cell =
           bacc + (size_t)c * NV + (size_t)slot * RC + a * SN_DEC_CELLS;
-      if (op == 0) acc192_add(x0, x1, x2, cell[0], cell[1], cell[2]);
-      else if (op == 1) x0 = cell[0] < x0 ? cell[0] : x0;
-      else x0 = cell[0] > x0 ? cell[0] : x0;
+      dec_fold(op, x0, x1, x2, cell[0], cell[1], cell[2]);
       cn += cell[3]; ov += cell[4];
     }
     dst += a * SN_DEC_CELLS;
@@ -2832,10 +2591,7 @@ void k_dec_reduce(const u64_t *__restrict__ scratch, int nblocks, int nslots,
   for (int b = lane; b < nblocks; b += 64) {
     const GAS u64_t *cell =
         src + (size_t)b * NV + (size_t)slot * RC + a * SN_DEC_CELLS;
-    const u64_t y0 = cell[0];
-    if (op == 0) acc192_add(x0, x1, x2, y0, cell[1], cell[2]);
-    else if (op == 1) x0 = y0 < x0 ? y0 : x0;
-    else x0 = y0 > x0 ? y0 : x0;
+    dec_fold(op, x0, x1, x2, cell[0], cell[1], cell[2]);
     c += cell[3]; o += cell[4];
   }
 #pragma unroll
@@ -2845,9 +2601,7 @@ void k_dec_reduce(const u64_t *__restrict__ scratch, int nblocks, int nslots,
     const u64_t y2 = __shfl_down(x2, off, 64);
     c += __shfl_down(c, off, 64);
     o += __shfl_down(o, off, 64);
-    if (op == 0) acc192_add(x0, x1, x2, y0, y1, y2);
-    else if (op == 1) x0 = y0 < x0 ? y0 : x0;
-    else x0 = y0 > x0 ? y0 : x0;
+    dec_fold(op, x0, x1, x2, y0, y1, y2);
   }
   if (lane == 0) {
     u64_t *dst = out + (size_t)slot * RC + a * SN_DEC_CELLS;
@@ -2866,17 +2620,12 @@ extern "C" int sn_launch_dec_scan(const sn_dev_plan *plan,
                                   void *stream) {
   hipStream_t s = (hipStream_t)stream;
   if (ntiles <= 0) return (int)hipErrorInvalidValue;
-  int grid;
-  if (ntiles <= SN_DEC_GRID_CAP) grid = ntiles;
-  else {
-    int rounds = (ntiles + SN_DEC_GRID_CAP - 1) / SN_DEC_GRID_CAP;
-    grid = (ntiles + rounds - 1) / rounds;
-  }
+  const int grid = sn_balanced_grid(ntiles, SN_DEC_GRID_CAP);
   const int keyless = plan->ngroup == 0;
   const int ns = keyless ? 1 : plan->nslots;
   const int na = dec->naggs;
   if (ns < 1 || na < 0 || na > 12) return (int)hipErrorInvalidValue;
-  if (sn_dec_lds_bytes(plan->nused, ns, na) > 160ull * 1024)
+  if (sn_dec_lds_bytes(plan->nused, ns, na) > SN_LDS_LIMIT)
     return (int)hipErrorInvalidValue;
   const int copies = keyless ? 1 : sn_dec_copies(plan->nused, ns, na);
   const size_t lds = (size_t)sn_dec_lds_bytes(plan->nused, ns * copies, na);
