@@ -284,6 +284,29 @@ int32_t sn_batch_put_raw(sn_engine *e, int32_t table, int64_t uuid,
 int64_t sn_table_num_batches(sn_engine *e, int32_t table);
 int64_t sn_table_num_rows(sn_engine *e, int32_t table);
 
+/* ---- low-cardinality f64 columns: 1-byte code sidecars ----
+ * At put time the engine tries to narrow every null-free uncompressed DOUBLE
+ * column of a batch: when the batch holds at most 256 distinct 64-bit value
+ * patterns, it keeps a num_rows-byte code array and a 256-entry dictionary
+ * beside the blob, and scans read 1 B/row instead of 8 (the f64 body stays
+ * resident for every other reader, so a narrowed column costs 1 B/row of
+ * extra HBM — about 3 B on lineitem's 34 B/row).  Results do not change:
+ * dictionary[code] is the body's exact bit pattern.  Any write to the body
+ * (update deltas at put or sn_batch_mutate) rebuilds or drops the sidecar.
+ * A query uses the codes for a column only when every batch it scans has
+ * them.  SN_NARROW=0 in the environment at sn_engine_create turns the
+ * feature off for that engine.
+ *
+ * sn_table_narrowed_batches: batches of `table` holding a live sidecar for
+ * column `col` (resolves pending device results first; -1 on bad args).
+ * sn_f64_narrow_host: the put-time kernels' contract in plain C++ — fits:
+ * dict[0..*ndict) = distinct patterns ascending as unsigned 64-bit integers,
+ * dict[*ndict..256) = 0, codes[i] = index of body[i]; more than 256
+ * patterns: *ndict = -1, dict[0..256) = 0, codes untouched. */
+int64_t sn_table_narrowed_batches(sn_engine *e, int32_t table, int32_t col);
+void    sn_f64_narrow_host(const double *body, int64_t n, uint8_t *codes,
+                           double *dict, int32_t *ndict);
+
 /* ---- dimension tables (row-store stand-in for the broadcast join) ----
  * The reference keeps dimension tables in the GemFire row store and builds
  * the probe map per task from region get()s; here the host holds the rows

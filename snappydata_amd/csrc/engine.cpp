@@ -194,6 +194,23 @@ struct Batch {
   const unsigned long long *stats_dev = nullptr;
   std::vector<uint8_t> is_raw;
   bool stats_pending = false;
+  /* 1-byte code sidecars of narrowed f64 columns: one arena
+   * block [256-entry dictionary][num_rows codes] per column, built on device
+   * at put; ndict > 0 = live, `pending` = the device result (a word of
+   * narrow_nd_dev) is not read yet — sync_pending_stats resolves it and
+   * returns overflowed blocks to the free list */
+  struct Narrow {
+    void *block = nullptr;
+    int32_t ndict = 0;
+    bool pending = false;
+    const double *dict() const { return (const double *)block; }
+    const uint8_t *codes() const {
+      return (const uint8_t *)block + SN_NARROW_MAX * 8;
+    }
+  };
+  std::vector<Narrow> narrow;
+  int32_t *narrow_nd_dev = nullptr;   /* [ncols] device entry counts */
+  bool narrow_pending = false;
   std::vector<ColMeta> cols;
   /* stats (parsed) */
   bool stats_valid = false;
@@ -279,6 +296,9 @@ struct sn_engine {
   std::vector<std::unique_ptr<Dim>> dims;
   hipStream_t stream = nullptr;
   bool has_gpu = false;
+  /* SN_NARROW (default on, 0 = off), read once per engine: narrow
+   * low-cardinality f64 columns into 1-byte code sidecars at put */
+  bool narrow = true;
   /* reusable per-engine scratch for block-partial reduction rows
    * (queries on one engine serialize on its stream) */
   double *scratch = nullptr;
@@ -354,6 +374,7 @@ extern "C" sn_engine *sn_engine_create(const sn_config *cfg) {
   if (e->cfg.hash_join_size <= 0) e->cfg.hash_join_size = 100ll << 20;
   if (e->cfg.shard_count <= 0) e->cfg.shard_count = 1;
   if (e->cfg.n_buckets <= 0) e->cfg.n_buckets = 128;
+  if (const char *nv = getenv("SN_NARROW")) e->narrow = nv[0] != '0';
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && e->cfg.device >= 0) {
     if (hipSetDevice(e->cfg.device) == hipSuccess &&
@@ -1063,6 +1084,96 @@ static void *up(sn_engine *e, const void *host, size_t n) {
   return d;
 }
 
+/* ---- f64 narrowing: 1-byte code sidecars built at put ---- */
+
+/* host reference of sn_launch_f64_narrow's contract (engine_internal.h) */
+extern "C" void sn_f64_narrow_host(const double *body, int64_t n,
+                                   uint8_t *codes, double *dict,
+                                   int32_t *ndict) {
+  std::vector<uint64_t> keys;          /* distinct patterns, kept ascending */
+  bool fits = true;
+  for (int64_t i = 0; i < n && fits; i++) {
+    uint64_t k;
+    memcpy(&k, &body[i], 8);
+    auto it = std::lower_bound(keys.begin(), keys.end(), k);
+    if (it != keys.end() && *it == k) continue;
+    if (keys.size() == SN_NARROW_MAX) fits = false;
+    else keys.insert(it, k);
+  }
+  memset(dict, 0, SN_NARROW_MAX * 8);
+  if (!fits) { *ndict = -1; return; }
+  if (!keys.empty()) memcpy(dict, keys.data(), keys.size() * 8);
+  *ndict = (int32_t)keys.size();
+  for (int64_t i = 0; i < n; i++) {
+    uint64_t k;
+    memcpy(&k, &body[i], 8);
+    codes[i] = (uint8_t)(std::lower_bound(keys.begin(), keys.end(), k) -
+                         keys.begin());
+  }
+}
+
+/* cheap host pre-filter where the put path holds the values: does a prefix
+ * of the column already carry more than 256 distinct patterns?  Then the
+ * device attempt (and the sidecar allocation) is skipped — l_extendedprice
+ * never allocates.  The device result decides for everything that passes. */
+static bool narrow_prefix_fits(const uint8_t *vals, int64_t n) {
+  const int64_t np = std::min<int64_t>(n, 4096);
+  uint64_t set[1024];
+  bool zero_seen = false;              /* 0 marks an empty slot */
+  memset(set, 0, sizeof(set));
+  int distinct = 0;
+  for (int64_t i = 0; i < np; i++) {
+    const uint64_t k = (uint64_t)rd_i64(vals + i * 8);
+    if (k == 0) { distinct += !zero_seen; zero_seen = true; continue; }
+    uint32_t h = (uint32_t)mix64h(k) & 1023u;
+    while (set[h] != 0 && set[h] != k) h = (h + 1) & 1023u;
+    if (set[h] == k) continue;
+    set[h] = k;
+    if (++distinct > SN_NARROW_MAX) return false;
+  }
+  return distinct <= SN_NARROW_MAX;
+}
+
+static size_t narrow_block_bytes(const Batch &b) {
+  return (size_t)SN_NARROW_MAX * 8 + (size_t)b.num_rows;
+}
+
+static void narrow_drop(sn_engine *e, Batch &b, int c) {
+  Batch::Narrow &nw = b.narrow[c];
+  if (nw.block) e->arena.release(nw.block, narrow_block_bytes(b));
+  nw = Batch::Narrow();
+}
+
+/* (re)build column c's sidecar from its device body, async on the engine
+ * stream behind whatever wrote the body; allocation or launch failure just
+ * leaves the column un-narrowed */
+static void narrow_launch(sn_engine *e, const Table *t, Batch &b, int c) {
+  if (!e->narrow || !e->has_gpu || b.num_rows <= 0) return;
+  const size_t nc = t->schema.size();
+  if (!b.narrow_nd_dev)
+    b.narrow_nd_dev = (int32_t *)e->arena.alloc(nc * 4);
+  Batch::Narrow &nw = b.narrow[c];
+  if (!nw.block) nw.block = e->arena.alloc(narrow_block_bytes(b));
+  if (!b.narrow_nd_dev || !nw.block) { narrow_drop(e, b, c); return; }
+  const double *body = (const double *)((const uint8_t *)b.col_dev[c] +
+                                        b.cols[c].body_off);
+  if (sn_launch_f64_narrow(body, b.num_rows, (unsigned char *)nw.codes(),
+                           (double *)nw.block, b.narrow_nd_dev + c,
+                           e->stream) != 0) {
+    narrow_drop(e, b, c);
+    return;
+  }
+  nw.ndict = 0;
+  nw.pending = true;
+  b.narrow_pending = true;
+}
+
+static bool narrow_eligible(const Table *t, const Batch &b, int c) {
+  return t->schema[c].dtype == SN_TYPE_DOUBLE &&
+         b.cols[c].type_id == SN_ENC_UNCOMPRESSED &&
+         b.cols[c].num_null_words == 0;
+}
+
 /* ---- batch mutation processing (shared by sn_batch_put and
  * sn_batch_mutate — the reference writes delete masks and delta blobs to
  * region entries of an EXISTING batch after UPDATE/DELETE statements;
@@ -1174,6 +1285,9 @@ static int32_t apply_deltas(sn_engine *e, Table *t, Batch &b,
                                     e->stream) == 0) {
             pd = Batch::PatchDev();
             P = Patch();
+            /* the body changed under the sidecar: rebuild it behind the
+             * patch kernel (an overflow drops it at the next query) */
+            if (k == SN_K_F64 && b.narrow[c].block) narrow_launch(e, t, b, c);
           }
         }
       }
@@ -1483,6 +1597,12 @@ static int32_t process_encoded_col(sn_engine *e, Table *t, Batch &b, int c,
       }
       b.nullpfx_dev[c] = (const uint32_t *)up(e, pfx.data(), pfx.size() * 4);
     }
+    /* low-cardinality doubles: code sidecar from the uploaded (or
+     * device-decoded) body */
+    if (narrow_eligible(t, b, c) &&
+        b.cols[c].body_off + (int64_t)b.num_rows * 8 <= len &&
+        narrow_prefix_fits(blob + b.cols[c].body_off, b.num_rows))
+      narrow_launch(e, t, b, c);
     return SN_OK;
 }
 
@@ -1518,6 +1638,7 @@ extern "C" int32_t sn_batch_put_raw(sn_engine *e, int32_t table,
   b.rle_vals_dev.resize(nc, nullptr);
   b.rle_n.resize(nc, 0);
   b.dictmap_cache.resize(nc);
+  b.narrow.resize(nc);
   b.is_raw.assign(nc, 0);
 
   unsigned long long *sd = nullptr;
@@ -1567,6 +1688,11 @@ extern "C" int32_t sn_batch_put_raw(sn_engine *e, int32_t table,
         return fail(SN_ERR_GENERIC, "stats kernel");
       b.is_raw[c] = 1;
       any_raw = true;
+      b.col_dev[c] = base + 8;
+      b.cols[c].body_off = 8;
+      if (dt == SN_TYPE_DOUBLE &&
+          narrow_prefix_fits((const uint8_t *)raw[c].data, num_rows))
+        narrow_launch(e, t, b, c);
     } else {
       int32_t hdr[2] = { SN_ENC_UNCOMPRESSED, 0 };
       memcpy(base + 8, hdr, 8);
@@ -1640,10 +1766,26 @@ extern "C" int32_t sn_batch_put_raw(sn_engine *e, int32_t table,
  * for ALL pending batches; called under t->mu before any bounds are read) */
 static void sync_pending_stats(sn_engine *e, Table *t) {
   bool any = false;
-  for (auto &b : t->batches) any |= b.stats_pending;
+  for (auto &b : t->batches) any |= b.stats_pending | b.narrow_pending;
   if (!any) return;
   (void)hipStreamSynchronize(e->stream);
   const int nc = (int)t->schema.size();
+  /* pending code sidecars: read the device entry counts; a column that
+   * overflowed (or whose readback failed) gives its block back */
+  std::vector<int32_t> nd((size_t)nc);
+  for (auto &b : t->batches) {
+    if (!b.narrow_pending) continue;
+    b.narrow_pending = false;
+    const bool got = hipMemcpy(nd.data(), b.narrow_nd_dev, (size_t)nc * 4,
+                               hipMemcpyDeviceToHost) == hipSuccess;
+    for (int c = 0; c < nc; c++) {
+      Batch::Narrow &nw = b.narrow[c];
+      if (!nw.pending) continue;
+      nw.pending = false;
+      if (got && nd[c] > 0 && nd[c] <= SN_NARROW_MAX) nw.ndict = nd[c];
+      else narrow_drop(e, b, c);
+    }
+  }
   std::vector<unsigned long long> h((size_t)nc * 2);
   for (auto &b : t->batches) {
     if (!b.stats_pending) continue;
@@ -1699,6 +1841,7 @@ extern "C" int32_t sn_batch_put(sn_engine *e, int32_t table,
   b.rle_vals_dev.resize(nc, nullptr);
   b.rle_n.resize(nc, 0);
   b.dictmap_cache.resize(nc);
+  b.narrow.resize(nc);
 
   /* Phase 1 — NO table lock: decompress, parse, validate, materialize and
    * upload are all batch-local (the arena has its own mutex), so concurrent
@@ -1819,6 +1962,16 @@ extern "C" int64_t sn_table_num_batches(sn_engine *e, int32_t table) {
 extern "C" int64_t sn_table_num_rows(sn_engine *e, int32_t table) {
   Table *t = get_table(e, table);
   return t ? t->total_rows : -1;
+}
+extern "C" int64_t sn_table_narrowed_batches(sn_engine *e, int32_t table,
+                                             int32_t col) {
+  Table *t = get_table(e, table);
+  if (!t || col < 0 || col >= (int32_t)t->schema.size()) return -1;
+  std::lock_guard<std::mutex> g(t->mu);
+  if (e->has_gpu) sync_pending_stats(e, t);
+  int64_t n = 0;
+  for (auto &b : t->batches) n += b.narrow[col].ndict > 0;
+  return n;
 }
 
 /* fetch back an engine-stored blob (tests / cross-validation) */
@@ -2439,7 +2592,8 @@ static int32_t build_dev_plan(sn_query *q, bool dec, sn_dev_plan &dp) {
  * (skipping is an optimization — correctness is unaffected either way).  An
  * uncacheable set's blocks belong to the query.  (The caller holds t->mu —
  * same critical section as the slot derivation.) */
-static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out) {
+static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp,
+                                bool narrow_ok, ScanSet *out) {
   sn_engine *e = q->e;
   Table *t = q->t;
   const sn_plan *plan = &q->plan;
@@ -2452,6 +2606,7 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out
   mix((uint64_t)(plan->join_dim + 3) * 29 + (uint64_t)plan->join_mode);
   mix((uint64_t)t->batches.size());
   for (auto &c : t->gdict) mix(c.size() * 7919);
+  mix(narrow_ok ? 0x6e617277ull : 0);
 
   int64_t skip_count = 0;
   for (auto &b : t->batches)
@@ -2488,6 +2643,23 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out
   const size_t nused = q->used_cols.size();
   DictPremul pm[SN_DEV_MAX_COLS];
   for (size_t ui = 0; ui < nused; ui++) pm[ui] = dict_premul(q, plan, q->used_cols[ui]);
+  /* a used f64 column scans from its 1-byte codes (SN_K_F64C8) only when
+   * EVERY unskipped batch holds a live sidecar for it; otherwise all its
+   * batches keep SN_K_F64 and the body, so kinds stay uniform per column
+   * (the JIT's rule) and one high-cardinality batch simply means the plain
+   * scan.  Decimal scans never narrow. */
+  bool narrow_col[SN_DEV_MAX_COLS];
+  for (size_t ui = 0; ui < nused; ui++) {
+    const int c = q->used_cols[ui];
+    bool all = narrow_ok && e->narrow &&
+               t->schema[c].dtype == SN_TYPE_DOUBLE;
+    for (auto &b : t->batches) {
+      if (!all) break;
+      if (skip_count && batch_skippable(b, plan, t)) continue;
+      all = b.narrow[c].ndict > 0;
+    }
+    narrow_col[ui] = all;
+  }
   for (auto &b : t->batches) {
     if (skip_count && batch_skippable(b, plan, t)) continue;
     sn_dev_batch db;
@@ -2499,6 +2671,13 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out
       int rc = fill_dev_col(e, t, b, q->used_cols[ui], pm[ui].mul,
                             pm[ui].null_gid, true, &db.cols[ui], &clean);
       if (rc != SN_OK) return rc;
+      if (narrow_col[ui]) {
+        const Batch::Narrow &nw = b.narrow[q->used_cols[ui]];
+        db.cols[ui].kind = SN_K_F64C8;
+        db.cols[ui].body = nw.codes();
+        db.cols[ui].rle_vals = nw.dict();
+        db.cols[ui].rle_n = nw.ndict;
+      }
     }
     db.clean = clean ? 1 : 0;
     for (size_t ui = 0; ui < nused; ui++)
@@ -2513,7 +2692,7 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp, ScanSet *out
       int k = jc.kind;
       bool stageable = k == SN_K_F64 || k == SN_K_I64 || k == SN_K_I32 ||
                        k == SN_K_F32 || k == SN_K_I16 || k == SN_K_DICT16 ||
-                       k == SN_K_DICT32;
+                       k == SN_K_DICT32 || k == SN_K_F64C8;
       if (!stageable || jc.has_nulls || jc.patch_n > 0) jit_ok = false;
       else if (jit_first) set.jit_kinds[ui] = k;
       else if (set.jit_kinds[ui] != k) jit_ok = false;
@@ -3016,7 +3195,8 @@ static sn_query *submit_impl(sn_engine *e, const sn_plan *plan,
   sn_dev_plan dp;
   if (build_dev_plan(q.get(), dec != nullptr, dp) != SN_OK) return nullptr;
   ScanSet set;
-  if (resolve_scan_set(q.get(), dp, &set) != SN_OK) return nullptr;
+  if (resolve_scan_set(q.get(), dp, dec == nullptr, &set) != SN_OK)
+    return nullptr;
   /* MIN/MAX plans always take the pac layout (per-agg counts carry the
    * empty-group NULL semantics; routing goes through the op-aware
    * grouped kernels, keyless included) */

@@ -35,13 +35,17 @@ enum {
   SN_K_U8 = 8,       /* uncompressed boolean byte body */
   SN_K_S8 = 9,       /* uncompressed int8 */
   SN_K_RLE = 10,     /* run-length: host-built run-ends + values aux */
-  SN_K_RLE_I64 = 11  /* run-length over an INT64 column: rle_vals carry the
+  SN_K_RLE_I64 = 11, /* run-length over an INT64 column: rle_vals carry the
                         RAW int64 bits memcpy'd into doubles (the LDS-image
                         convention for i64), not numeric doubles.
                         (Int-typed DICTIONARY columns have no kernel kind:
                         the host materializes their values into a plain
                         fixed-width body at put — decompress-on-put, like
                         the LZ4 wrapper.) */
+  SN_K_F64C8 = 12    /* narrowed double: body = 1-byte codes (the put-time
+                        sidecar, not the blob), rle_vals = the batch's value
+                        dictionary of rle_n <= 256 doubles, value =
+                        rle_vals[body[row]] — bit for bit the f64 body's */
 };
 
 typedef struct {
@@ -545,6 +549,21 @@ int sn_launch_lz4_decompress(const void *src, long long slen, void *dst,
 int sn_launch_col_minmax(const void *body, long long n, int kind,
                          unsigned long long *omin, unsigned long long *omax,
                          void *stream);
+
+/* put-time narrowing of one null-free f64 body into 1-byte codes and a
+ * dictionary of at most SN_NARROW_MAX doubles; async on `stream`, no host
+ * sync.  Values are told apart by their 64-bit pattern (-0.0 and +0.0, and
+ * every NaN payload, are entries of their own).
+ *   fits:     dict[0..*ndict) = the distinct patterns ascending as unsigned
+ *             64-bit integers, dict[*ndict..256) = 0, codes[i] = index of
+ *             body[i]'s pattern;
+ *   overflow: (> 256 patterns) *ndict = -1, dict[0..256) = 0, codes untouched
+ *             — the encode kernel reads *ndict on device and returns.
+ * Writes nothing outside [codes, codes + n), dict[0..256) and *ndict.
+ * sn_f64_narrow_host (snappy_engine.h) is the same contract in plain C++. */
+#define SN_NARROW_MAX 256
+int sn_launch_f64_narrow(const double *body, long long n, unsigned char *codes,
+                         double *dict, int *ndict, void *stream);
 
 /* launches only the partial-fold (k_reduce): scratch[nblocks][nv] -> out.
  * Used by the JIT path, whose scan kernel writes the same scratch rows.

@@ -239,14 +239,16 @@ static JitShape jit_classify(const sn_dev_plan *p, const int *kinds,
  * All the generator knows about a stageable column kind.  A chunk of a
  * column is staged as two registers per lane, two rows each: st<c>_0 holds
  * rows 2*tid(+1), st<c>_1 rows 2*(tid+WG)(+1); 16-bit kinds pack their two
- * rows into one unsigned.  The LDS image holds every value as a double,
+ * rows into one unsigned, the 1-byte kind both into one unsigned short.
+ * The LDS image holds every value as a double,
  * except that 8-byte kinds keep their raw bits (an i64 converts where it is
  * read, by the plan's i64_mask). */
 enum JitConv {
   CV_BITS64,   /* the 8 bytes as they are */
   CV_NUM,      /* numeric cast */
   CV_F32,      /* float bits in an int register */
-  CV_DICT      /* dm<c>[index]: premultiplied dictionary contribution */
+  CV_DICT,     /* dm<c>[index]: premultiplied dictionary contribution */
+  CV_VDICT     /* vd<c>[code]: the batch's value dictionary of doubles */
 };
 struct JitKind {
   const char *reg;   /* register type of one staged load */
@@ -265,6 +267,8 @@ static const JitKind &jit_kind(int k) {
   static const JitKind d32 = { "int2_t", 4, "int", CV_DICT, 0, 0 };
   static const JitKind d16 = { "unsigned", 2, "unsigned short", CV_DICT, 0, 0 };
   static const JitKind i16 = { "unsigned", 2, "short", CV_NUM, 0, 0 };
+  static const JitKind c8 = { "unsigned short", 1, "unsigned char", CV_VDICT,
+                              0, 0 };
   switch (k) {
     case SN_K_F64: return f64;
     case SN_K_I64: return i64;
@@ -272,6 +276,7 @@ static const JitKind &jit_kind(int k) {
     case SN_K_F32: return f32;
     case SN_K_DICT32: return d32;
     case SN_K_DICT16: return d16;
+    case SN_K_F64C8: return c8;
     default: return i16;   /* SN_K_I16; the engine stages no other kind */
   }
 }
@@ -281,6 +286,8 @@ static const JitKind &jit_kind(int k) {
 static std::string kind_reg_row(const JitKind &K, int c, int j) {
   if (K.bytes == 2)
     return strf((j & 1) ? "st%d_%d >> 16" : "st%d_%d & 0xffff", c, j >> 1);
+  if (K.bytes == 1)
+    return strf((j & 1) ? "st%d_%d >> 8" : "st%d_%d & 0xff", c, j >> 1);
   return strf("st%d_%d.%s", c, j >> 1, (j & 1) ? "y" : "x");
 }
 
@@ -291,6 +298,7 @@ static std::string kind_image_from_reg(const JitKind &K, int c, int j) {
   switch (K.conv) {
     case CV_BITS64: return r;
     case CV_DICT: return strf("(double)dm%d[%s]", c, r.c_str());
+    case CV_VDICT: return strf("vd%d[%s]", c, r.c_str());
     case CV_F32: return strf("(double)f%d.%s", j >> 1, (j & 1) ? "y" : "x");
     default:
       return K.bytes == 2 ? strf("(double)(short)(%s)", r.c_str())
@@ -319,6 +327,7 @@ static std::string kind_image_from_mem(const JitKind &K, int c) {
     case CV_DICT:
       return strf("(double)dm%d[%s%s]", c, K.bytes == 2 ? "(int)" : "",
                   m.c_str());
+    case CV_VDICT: return strf("vd%d[%s]", c, m.c_str());
     default: return strf("(double)%s", m.c_str());
   }
 }
@@ -633,6 +642,8 @@ static void emit_tile_prologue(Gen &g) {
     emitf(o, "    const GAS char *body%d = (const GAS char *)(unsigned long long)b.cols[%d].body;\n", c, c);
     if (jit_kind(g.kinds[c]).conv == CV_DICT)
       emitf(o, "    const GAS int *dm%d = (const GAS int *)(unsigned long long)b.cols[%d].dictmap;\n", c, c);
+    if (jit_kind(g.kinds[c]).conv == CV_VDICT)
+      emitf(o, "    const GAS double *vd%d = (const GAS double *)(unsigned long long)b.cols[%d].rle_vals;\n", c, c);
   }
 }
 
@@ -1120,6 +1131,15 @@ static std::string gen_source(const sn_dev_plan *p, const int *kinds,
   const bool radix = g.s.acc == ACC_RADIX;
 
   emit_prelude(o);
+  /* a value-dictionary column reads one more descriptor member; its pin is
+   * emitted with it, so kernels without such a column keep their text */
+  for (int c = 0; c < g.s.NC; c++)
+    if (jit_kind(kinds[c]).conv == CV_VDICT) {
+      emitf(o, "static_assert(__builtin_offsetof(sn_dev_col, rle_vals) == %zu, "
+               "\"layout mirror differs from engine_internal.h\");\n",
+            offsetof(sn_dev_col, rle_vals));
+      break;
+    }
   emit_signature(g);
   emit_literals(g);
   emit_acc_decl(g);

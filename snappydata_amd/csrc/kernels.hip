@@ -92,7 +92,9 @@ __device__ __forceinline__ int read_general(const sn_dev_col &c, int row,
         *gid = (int)__double2ll_rn(pv);
         return 1;
       }
-      if (c.kind == SN_K_F64 || c.kind == SN_K_F32) { *vd = pv; *vi = (long long)pv; }
+      if (c.kind == SN_K_F64 || c.kind == SN_K_F32 || c.kind == SN_K_F64C8) {
+        *vd = pv; *vi = (long long)pv;
+      }
       else if (c.kind == SN_K_I64 || c.kind == SN_K_RLE_I64) {
         /* INT64 patch values travel as RAW BITS (decode_delta keeps them
          * exact beyond 2^53); vd keeps the raw-bit double so the LDS image
@@ -119,6 +121,10 @@ __device__ __forceinline__ int read_general(const sn_dev_col &c, int row,
     case SN_K_BOOLBIT: *vi = bm_get((const uint64_t *)c.body, nnp); *vd = (double)*vi; break;
     case SN_K_U8: *vi = as_global((const uint8_t *)c.body)[nnp] == 1; *vd = (double)*vi; break;
     case SN_K_S8: *vi = as_global((const int8_t *)c.body)[nnp]; *vd = (double)*vi; break;
+    case SN_K_F64C8:   /* 1-byte code into the batch's value dictionary */
+      *vd = as_global(c.rle_vals)[as_global((const uint8_t *)c.body)[nnp]];
+      *vi = (long long)*vd;
+      break;
     case SN_K_RLE:
       *vd = rle_value(c, nnp);
       *vi = __double2ll_rn(*vd);        /* numeric doubles (i16/i32 runs) */
@@ -254,6 +260,16 @@ __device__ __forceinline__ void convert_chunk(
           }
           break;
         }
+        case SN_K_F64C8: {
+          const GAS uint8_t *src = as_global((const uint8_t *)col.body) + base;
+          const GAS double *vd = as_global(col.rle_vals);
+#pragma unroll
+          for (int k = 0; k < CHUNK / WG; k++) {
+            int r = tid + k * WG;
+            if (r < rows) dst[r] = vd[src[r]];
+          }
+          break;
+        }
         case SN_K_RLE:
         case SN_K_RLE_I64: {
           /* RLE_I64 run values are raw i64 bits as doubles — exactly the
@@ -332,8 +348,11 @@ __device__ __forceinline__ void hoist_cols(const sn_dev_batch &b, int nused,
 #pragma unroll
   for (int c = 0; c < NC; c++) {
     cr[c].body = c < nused ? b.cols[c].body : nullptr;
-    cr[c].dictmap = c < nused ? b.cols[c].dictmap : nullptr;
     cr[c].kind = c < nused ? b.cols[c].kind : -1;
+    /* a code column keeps its value dictionary (doubles) in the map slot */
+    cr[c].dictmap = c >= nused ? nullptr
+        : cr[c].kind == SN_K_F64C8 ? (const int32_t *)b.cols[c].rle_vals
+                                   : b.cols[c].dictmap;
   }
 }
 
@@ -353,6 +372,7 @@ __device__ __forceinline__ int col_width_class(int kind) {
     case SN_K_F64: case SN_K_I64: return 8;
     case SN_K_I32: case SN_K_F32: case SN_K_DICT32: return 4;
     case SN_K_I16: case SN_K_DICT16: return 2;
+    case SN_K_F64C8: return 1;
     default: return 0;   /* BOOLBIT: not stageable */
   }
 }
@@ -379,6 +399,12 @@ __device__ __forceinline__ void stage_load(const ColRegs (&cr)[NC], int nused,
       int2_t a0 = s2[tid], a1 = s2[tid + WG];
       st.buf[NB == 1 ? 0 : c][0].x = *(double *)&a0;
       st.buf[NB == 1 ? 0 : c][0].y = *(double *)&a1;
+    } else if (w == 1) {
+      /* two 2 B pair-loads -> packed into the low word of buf[c][0].x */
+      const GAS unsigned short *s2 = (const GAS unsigned short *)
+          as_global((const char *)col.body + (size_t)base);
+      unsigned a0 = s2[tid], a1 = s2[tid + WG];
+      st.buf[NB == 1 ? 0 : c][0].x = pack_u64(a0 | (a1 << 16), 0u);
     } else {
       /* two short2 (4 B) pair-loads -> packed into buf[c][0].x */
       const GAS unsigned *s2 = (const GAS unsigned *)
@@ -434,6 +460,19 @@ __device__ __forceinline__ void stage_write(const ColRegs (&cr)[NC], int nused,
             y.x = (double)dm[(int)(uint16_t)e0];
             y.y = (double)dm[(int)(uint16_t)e1];
           }
+          ((double2_t *)dst)[tid + p * WG] = y;
+        }
+        break;
+      }
+      case SN_K_F64C8: {
+        const GAS double *vd = (const GAS double *)as_global(col.dictmap);
+        unsigned raw = (unsigned)__double_as_longlong(st.buf[NB == 1 ? 0 : c][0].x);
+#pragma unroll
+        for (int p = 0; p < CHUNK / (2 * WG); p++) {
+          unsigned half = (raw >> (16 * p)) & 0xffffu;
+          double2_t y;
+          y.x = vd[half & 0xff];
+          y.y = vd[half >> 8];
           ((double2_t *)dst)[tid + p * WG] = y;
         }
         break;
@@ -1933,6 +1972,191 @@ extern "C" int sn_launch_col_minmax(const void *body, long long n, int kind,
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(k_col_minmax, dim3((unsigned)blocks), dim3(256), 0,
                      (hipStream_t)stream, body, n, kind, omin, omax);
+  return (int)hipGetLastError();
+}
+
+/* ---- put-time f64 narrowing: 1-byte codes + a value dictionary ----
+ * A low-cardinality double column (TPC-H l_quantity: 50 values, l_discount:
+ * 11) scans from a num_rows-byte code array and a <= 256-entry dictionary
+ * instead of its 8 B/row body.  Values are told apart by
+ * their 64-bit PATTERN, so -0.0 / +0.0 and every NaN payload are entries of
+ * their own and dict[code] gives back the exact input bits.
+ *
+ * Three launches, async on the ingest stream, no host sync:
+ *   k_f64_distinct  every workgroup inserts its grid-stride slice into an
+ *                   LDS open-address set, gives up once that holds more than
+ *                   256 patterns, else merges it into the global set;
+ *   k_f64_dict      one workgroup compacts and rank-sorts the global set
+ *                   (ascending as unsigned integers) into dict[0..ndict) and
+ *                   zeroes the rest, or writes ndict = -1 and zeroes it all;
+ *   k_f64_encode    reads ndict on device, returns when it is negative, else
+ *                   binary-searches an LDS copy of the dictionary per row.
+ * The global set IS dict[0..256) (u64 view) and the flags live in *ndict, so
+ * the launcher needs no workspace and nothing outside [codes, codes+n),
+ * dict[0..256) and *ndict is ever written.  All 2^64 patterns are values, so
+ * the empty-slot sentinel (all ones, itself a NaN payload) is tracked by a
+ * flag instead of being stored. */
+#define NARROW_MAX 256            /* dictionary entries == global set slots */
+#define NARROW_LSLOTS 2048        /* LDS set: <= 256 + one 1024-row step */
+#define NARROW_STEP 4             /* rows per lane per step */
+#define NARROW_EMPTY (~0ull)
+#define NARROW_F_OVERFLOW (1 << 30)
+#define NARROW_F_HAS_EMPTY (1 << 29)
+
+__global__ __launch_bounds__(WG, 4)
+void k_f64_distinct(const double *__restrict__ body_, long long n,
+                    double *__restrict__ dict_, int *__restrict__ ndict_) {
+  __shared__ unsigned long long lset[NARROW_LSLOTS];
+  __shared__ int lcount, lflags;
+  const GAS unsigned long long *body =
+      (const GAS unsigned long long *)(uintptr_t)body_;
+  unsigned long long *gset = (unsigned long long *)dict_;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < NARROW_LSLOTS; i += WG) lset[i] = NARROW_EMPTY;
+  if (tid == 0) { lcount = 0; lflags = 0; }
+  __syncthreads();
+  const long long span = (long long)WG * NARROW_STEP;
+  for (long long base = (long long)blockIdx.x * span; base < n;
+       base += (long long)gridDim.x * span) {
+    unsigned long long v[NARROW_STEP];
+#pragma unroll
+    for (int j = 0; j < NARROW_STEP; j++) {
+      const long long i = base + tid + (long long)j * WG;
+      v[j] = i < n ? body[i] : body[base];   /* base < n: a value of the slice */
+    }
+#pragma unroll
+    for (int j = 0; j < NARROW_STEP; j++) {
+      const unsigned long long key = v[j];
+      if (key == NARROW_EMPTY) { atomicOr(&lflags, NARROW_F_HAS_EMPTY); continue; }
+      /* the set holds at most 256 + 1024 of its 2048 slots, so a probe
+       * always meets the key or an empty slot */
+      unsigned h = (unsigned)mix64(key) & (NARROW_LSLOTS - 1);
+      while (true) {
+        unsigned long long k0 = lset[h];
+        if (k0 == key) break;
+        if (k0 == NARROW_EMPTY) {
+          k0 = atomicCAS(&lset[h], NARROW_EMPTY, key);
+          if (k0 == NARROW_EMPTY) { atomicAdd(&lcount, 1); break; }
+          if (k0 == key) break;
+        }
+        h = (h + 1) & (NARROW_LSLOTS - 1);
+      }
+    }
+    __syncthreads();
+    if (lcount > NARROW_MAX) break;          /* uniform: lcount is settled */
+    __syncthreads();                         /* before the next step's adds */
+  }
+  if (lcount > NARROW_MAX) {
+    if (tid == 0) atomicOr(ndict_, NARROW_F_OVERFLOW);
+    return;
+  }
+  if (tid == 0 && lflags) atomicOr(ndict_, lflags);
+  for (int i = tid; i < NARROW_LSLOTS; i += WG) {
+    const unsigned long long key = lset[i];
+    if (key == NARROW_EMPTY) continue;
+    unsigned h = (unsigned)mix64(key) & (NARROW_MAX - 1);
+    int it = 0;
+    for (; it < NARROW_MAX; it++) {
+      /* a slot only ever goes from empty to its key, so a plain look first
+       * is safe however stale, and spares the hot lines all but the first
+       * workgroups' atomics (every workgroup brings the same few keys) */
+      unsigned long long k0 = __hip_atomic_load(
+          &gset[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (k0 == NARROW_EMPTY) k0 = atomicCAS(&gset[h], NARROW_EMPTY, key);
+      if (k0 == NARROW_EMPTY || k0 == key) break;
+      h = (h + 1) & (NARROW_MAX - 1);
+    }
+    if (it == NARROW_MAX) atomicOr(ndict_, NARROW_F_OVERFLOW);   /* set full */
+  }
+}
+
+__global__ __launch_bounds__(NARROW_MAX, 1)
+void k_f64_dict(double *__restrict__ dict_, int *__restrict__ ndict_) {
+  __shared__ unsigned long long keys[NARROW_MAX], sorted[NARROW_MAX];
+  __shared__ int nvalid;
+  unsigned long long *gset = (unsigned long long *)dict_;
+  const int tid = threadIdx.x;
+  const int flags = *ndict_;
+  const unsigned long long key = gset[tid];
+  keys[tid] = key;
+  sorted[tid] = 0;
+  if (tid == 0) nvalid = 0;
+  __syncthreads();
+  const int valid = key != NARROW_EMPTY;
+  if (valid) atomicAdd(&nvalid, 1);
+  /* distinct keys: the count of smaller ones is the sorted position */
+  int rank = 0;
+  for (int j = 0; j < NARROW_MAX; j++)
+    rank += (keys[j] != NARROW_EMPTY) & (keys[j] < key);
+  __syncthreads();
+  const int has_empty = (flags & NARROW_F_HAS_EMPTY) != 0;
+  const int total = nvalid + has_empty;
+  const int fits = !(flags & NARROW_F_OVERFLOW) && total <= NARROW_MAX;
+  if (fits) {
+    if (valid) sorted[rank] = key;
+    /* all ones is the largest pattern: it sorts last */
+    if (has_empty && tid == 0) sorted[total - 1] = NARROW_EMPTY;
+  }
+  __syncthreads();
+  gset[tid] = sorted[tid];
+  if (tid == 0) *ndict_ = fits ? total : -1;
+}
+
+__global__ __launch_bounds__(WG, 4)
+void k_f64_encode(const double *__restrict__ body_, long long n,
+                  unsigned char *__restrict__ codes_,
+                  const double *__restrict__ dict_,
+                  const int *__restrict__ ndict_) {
+  __shared__ unsigned long long sd[NARROW_MAX];
+  const int nd = *ndict_;
+  if (nd < 0) return;                        /* overflow: codes stay untouched */
+  const GAS unsigned long long *body =
+      (const GAS unsigned long long *)(uintptr_t)body_;
+  GAS unsigned char *codes = (GAS unsigned char *)(uintptr_t)codes_;
+  const int tid = threadIdx.x;
+  sd[tid] = ((const unsigned long long *)dict_)[tid];
+  __syncthreads();
+  auto code_of = [&](unsigned long long key) {
+    int pos = 0;                             /* entries [0, pos) are < key */
+#pragma unroll
+    for (int s = NARROW_MAX / 2; s > 0; s >>= 1) {
+      const int p = pos + s;
+      if (p <= nd && sd[p - 1] < key) pos = p;
+    }
+    return (unsigned)pos;
+  };
+  /* aligned code arrays (every arena block) store four codes per lane */
+  const int packed = ((uintptr_t)codes_ & 3) == 0;
+  const long long n4 = packed ? n / 4 : 0;
+  const long long stride = (long long)gridDim.x * WG;
+  for (long long g = (long long)blockIdx.x * WG + tid; g < n4; g += stride) {
+    unsigned w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) w |= code_of(body[g * 4 + j]) << (8 * j);
+    ((GAS unsigned *)codes)[g] = w;
+  }
+  for (long long i = n4 * 4 + (long long)blockIdx.x * WG + tid; i < n;
+       i += stride)
+    codes[i] = (unsigned char)code_of(body[i]);
+}
+
+extern "C" int sn_launch_f64_narrow(const double *body, long long n,
+                                    unsigned char *codes, double *dict,
+                                    int *ndict, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t rc = hipMemsetAsync(dict, 0xff, NARROW_MAX * 8, s);
+  if (rc == hipSuccess) rc = hipMemsetAsync(ndict, 0, 4, s);
+  if (rc != hipSuccess) return (int)rc;
+  const long long span = (long long)WG * NARROW_STEP;
+  long long blocks = (n + span - 1) / span;
+  if (blocks > 1024) blocks = 1024;
+  if (blocks > 0)
+    hipLaunchKernelGGL(k_f64_distinct, dim3((unsigned)blocks), dim3(WG), 0, s,
+                       body, n, dict, ndict);
+  hipLaunchKernelGGL(k_f64_dict, dim3(1), dim3(NARROW_MAX), 0, s, dict, ndict);
+  if (blocks > 0)
+    hipLaunchKernelGGL(k_f64_encode, dim3((unsigned)blocks), dim3(WG), 0, s,
+                       body, n, codes, dict, ndict);
   return (int)hipGetLastError();
 }
 

@@ -72,6 +72,12 @@ def lib():
         L.sn_table_num_batches.argtypes = [C.c_void_p, C.c_int32]
         L.sn_table_num_rows.restype = C.c_int64
         L.sn_table_num_rows.argtypes = [C.c_void_p, C.c_int32]
+        L.sn_table_narrowed_batches.restype = C.c_int64
+        L.sn_table_narrowed_batches.argtypes = [C.c_void_p, C.c_int32,
+                                                C.c_int32]
+        L.sn_f64_narrow_host.restype = None
+        L.sn_f64_narrow_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
         L.sn_table_get_blob.restype = C.c_int64
         L.sn_table_get_blob.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_void_p, C.c_int64]
@@ -236,6 +242,19 @@ def dec_avg(total, count, scale=0):
     out = abi.SnDecVal()
     _check(lib().sn_dec_avg(C.byref(v), count, C.byref(out)), "dec_avg")
     return abi.dec_int(out), out.scale
+
+
+def f64_narrow_host(values, fill=0):
+    """sn_f64_narrow_host on a float64 array: (codes uint8[n] pre-filled with
+    `fill`, dict float64[256], ndict) — the CPU reference of the put-time
+    narrowing kernels."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    codes = np.full(v.size, fill, dtype=np.uint8)
+    d = np.empty(256, dtype=np.float64)
+    nd = C.c_int32(0)
+    lib().sn_f64_narrow_host(v.ctypes.data, v.size, codes.ctypes.data,
+                             d.ctypes.data, C.byref(nd))
+    return codes, d, nd.value
 
 
 def gen_lineitem_arrays(start_row, n, seed):
@@ -438,6 +457,12 @@ class Engine:
 
     def num_rows(self, table):
         return _check(lib().sn_table_num_rows(self._h, table))
+
+    def narrowed_batches(self, table, col):
+        """Batches holding a live 1-byte code sidecar for f64 column `col`
+        (built at put for columns of at most 256 distinct values; off with
+        SN_NARROW=0 in the environment when the engine is created)."""
+        return _check(lib().sn_table_narrowed_batches(self._h, table, col))
 
     def get_blob(self, table, batch, col, cap=1 << 26):
         buf = np.zeros(cap, dtype=np.uint8)
