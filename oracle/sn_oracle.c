@@ -886,6 +886,13 @@ static void gtab_rehash(sno_gtab *g) {
   g->index_cap = ncap;
 }
 
+/* MAX under the aggregates' order (Spark Max: NaN is greater than every
+ * other value, +inf included; fmax would drop it).  MIN needs no twin: fmin
+ * returns the other side of a NaN, so it is NaN only when both are. */
+static double agg_max(double a, double b) {
+  return (a != a || b != b) ? NAN : fmax(a, b);
+}
+
 static sno_group *gtab_get(sno_gtab *g, const char (*keys)[SN_KEY_MAX],
                            const uint8_t *knull) {
   if (g->n * 2 >= g->index_cap) gtab_rehash(g);
@@ -1109,7 +1116,7 @@ static int eval_batch(const sno_table *t, const sno_batch *b, const sn_plan *p,
         if (ag->kind == SN_AGG_MIN)
           grp->sums[a] = grp->counts[a] > 0 ? fmin(grp->sums[a], v) : v;
         else if (ag->kind == SN_AGG_MAX)
-          grp->sums[a] = grp->counts[a] > 0 ? fmax(grp->sums[a], v) : v;
+          grp->sums[a] = grp->counts[a] > 0 ? agg_max(grp->sums[a], v) : v;
         else
           grp->sums[a] += v;
         grp->counts[a] += 1.0;
@@ -1401,7 +1408,7 @@ static int32_t sno_run(sno_table *t, const sn_plan *p, int32_t nthreads,
             if (src->counts[a] > 0)
               dst->sums[a] = dst->counts[a] > 0
                   ? (k == SN_AGG_MIN ? fmin(dst->sums[a], src->sums[a])
-                                     : fmax(dst->sums[a], src->sums[a]))
+                                     : agg_max(dst->sums[a], src->sums[a]))
                   : src->sums[a];
           } else {
             dst->sums[a] += src->sums[a];

@@ -41,6 +41,7 @@
 #include <cstdio>
 #include <cstring>
 #include <malloc.h>
+#include <limits>
 #include <map>
 #include <set>
 #include <memory>
@@ -3751,6 +3752,10 @@ extern "C" int32_t sn_query_order_by(sn_query *q, int32_t agg_idx,
                        bool ha = val_of(a, &va), hb = val_of(b, &vb);
                        if (ha != hb) return ha;                 /* NULLs last */
                        if (!ha) return false;
+                       /* a strict weak order with NaN in it: every NaN is
+                        * one value above +inf */
+                       const bool na = va != va, nb = vb != vb;
+                       if (na || nb) return descending ? na && !nb : nb && !na;
                        return descending ? va > vb : va < vb;
                      });
   } else {
@@ -3966,11 +3971,15 @@ extern "C" int32_t sn_query_merge(sn_query *q, const void *blocks, int64_t strid
   auto fold = [&](GroupOut &g, int a, double s, double c) {
     int k = p.aggs[a].kind;
     if (k == SN_AGG_MIN || k == SN_AGG_MAX) {
+      /* the aggregates' order: NaN above +inf (std::min/std::max would
+       * keep whichever side came first once a NaN is involved).  fmin
+       * returns the other side of a NaN, which is MIN's rule already. */
       if (c > 0)
-        g.sums[a] = g.counts[a] > 0
-                        ? (k == SN_AGG_MIN ? std::min(g.sums[a], s)
-                                           : std::max(g.sums[a], s))
-                        : s;
+        g.sums[a] = g.counts[a] <= 0 ? s
+                    : k == SN_AGG_MIN ? fmin(g.sums[a], s)
+                    : (g.sums[a] != g.sums[a] || s != s)
+                        ? std::numeric_limits<double>::quiet_NaN()
+                        : fmax(g.sums[a], s);
     } else {
       g.sums[a] += s;
     }

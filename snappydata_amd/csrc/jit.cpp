@@ -447,6 +447,38 @@ __device__ __forceinline__ u64 mix64(u64 x) {
              "engine_internal.h\");\n", pin.what, pin.is);
 }
 
+/* MIN/MAX order values by the aggregates' total order (non-finite
+ * aggregate inputs): f64ord's, with every NaN, whatever its sign and payload,
+ * one value above +inf.  Its image, that of the positive quiet NaN, is also
+ * MIN's identity.  Emitted into kernels with a MIN/MAX aggregate only, the
+ * wave folds into the register mode only, so every other kernel keeps its
+ * text. */
+static void emit_order_helpers(Gen &g) {
+  if (!g.s.mm_any) return;
+  g.o += R"(__device__ __forceinline__ u64 f64ordc(double x) {
+  return x != x ? 0xFFF8000000000000ull : f64ord(x);
+}
+)";
+  if (g.s.acc != ACC_REGS) return;
+  g.o += R"(__device__ __forceinline__ u64 wminu(u64 x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 y = (u64)__shfl_down((i64)x, off, 64);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+__device__ __forceinline__ u64 wmaxu(u64 x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 y = (u64)__shfl_down((i64)x, off, 64);
+    x = y > x ? y : x;
+  }
+  return x;
+}
+)";
+}
+
 static void emit_signature(Gen &g) {
   emitf(g.o, "extern \"C\" __global__ __launch_bounds__(WG, %d)\n"
            "void jit_scan(const sn_dev_batch *__restrict__ batches,\n"
@@ -574,13 +606,19 @@ static void emit_acc_decl(Gen &g) {
     case ACC_REGS:
       emitf(o, bacc, s.nv);
       emitf(d, "  double sums[%d][%d]; double rc[%d];\n", s.NS, s.NA, s.NS);
+      if (s.mm_any) emitf(d, "  u64 ords[%d][%d];\n", s.NS, s.NA);
+      /* the block accumulator starts here, not at the flush: non-finite
+       * values reach it during the scan */
+      emit_acc_init(d, g, "bacc", s.nv, s.mm_any);
       emitf(d, "#pragma unroll\n  for (int s = 0; s < %d; s++) {\n"
                "    rc[s] = 0;\n", s.NS);
+      /* a MIN/MAX aggregate keeps the order image of its value in ords,
+       * a sum its double in sums; the unused half of each pair folds away */
       for (int a = 0; a < s.NA; a++) {
         const int op = g.p->aggs[a].op;
         if (op == 0) emitf(d, "    sums[s][%d] = 0.0;\n", a);
-        else emitf(d, "    sums[s][%d] = __longlong_as_double(%s);\n", a,
-                   op == 1 ? "0x7FF0000000000000ll" : "0xFFF0000000000000ll");
+        else emitf(d, "    ords[s][%d] = %s;\n", a,
+                   op == 1 ? "0xFFF8000000000000ull" : "0ull");
       }
       d += "  }\n";
       break;
@@ -948,7 +986,8 @@ static void emit_agg_values(Gen &g) {
   for (int a = 0; a < g.s.NA; a++) {
     const sn_dev_agg &A = g.p->aggs[a];
     if (A.nf < 1) { emitf(o, "        const double va%d = 1.0;\n", a); continue; }
-    emitf(o, "        const double va%d = %s", a,
+    /* the register mode replaces a non-finite value before its fma */
+    emitf(o, "        %sdouble va%d = %s", g.s.acc == ACC_REGS ? "" : "const ", a,
           factor(a, 0, A.c0, A.a0, A.m0).c_str());
     if (A.nf >= 2) emitf(o, " * %s", factor(a, 1, A.c1, A.a1, A.m1).c_str());
     if (A.nf >= 3) emitf(o, " * %s", factor(a, 2, A.c2, A.a2, A.m2).c_str());
@@ -976,7 +1015,7 @@ static void emit_accumulate(Gen &g) {
         if (op == 0)
           emitf(o, "          atomicAdd((double *)&row[%d], va%d);\n", a, a);
         else
-          emitf(o, "          %s((unsigned long long *)&row[%d], f64ord(va%d));\n",
+          emitf(o, "          %s((unsigned long long *)&row[%d], f64ordc(va%d));\n",
                 op == 1 ? "atomicMin" : "atomicMax", a, a);
         if (g.p->pac)
           emitf(o, "          atomicAdd((double *)&row[%d], 1.0);\n", s.NA + a);
@@ -991,12 +1030,40 @@ static void emit_accumulate(Gen &g) {
         emitf(o, "          atomicAdd(&row[%d], va%d);\n", a, a);
       o += "        }\n";
       break;
-    case ACC_REGS:
-      /* m is 0.0 or 1.0; fma(m, va, sum) is bit-identical to the select+add
-       * form (m=0 -> sum exactly, m=1 -> one rounding like the add) but one
-       * VALU op per aggregate instead of two */
+    case ACC_REGS: {
+      /* Each row adds to its own slot alone, and a row that did not pass to
+       * none.  With m = 0.0 or 1.0, fma(m, va, sum) does that in one VALU op
+       * per slot and aggregate where select + add takes three, and is
+       * bit-identical to it (m = 0 leaves sum, m = 1 rounds once like the
+       * add), but only for finite va: fma(0, +-inf or NaN, sum) is NaN, so
+       * one such value, of a filtered row included, would turn every slot of
+       * the lane NaN.  One compare per aggregate and row finds those values.
+       * An iteration in which some lane of the wave holds one adds the
+       * passing ones straight into the block accumulator (zeroed at kernel
+       * entry, LDS atomics) and hands the fma a 0.0 in their place.  The
+       * rare block writes no register accumulator, so the common path keeps
+       * the registers and the schedule it had without the check. */
+      std::string nonfin;
+      for (int a = 0; a < s.NA; a++)
+        if (g.p->aggs[a].op == 0 && g.p->aggs[a].nf >= 1)
+          nonfin += strf("%s!(__builtin_fabs(va%d) <= 1.7976931348623157e308)",
+                         nonfin.empty() ? "" : " |\n            ", a);
+      if (!nonfin.empty()) {
+        emitf(o, "        if (__ballot(%s)) {\n", nonfin.c_str());
+        for (int a = 0; a < s.NA; a++)
+          if (g.p->aggs[a].op == 0 && g.p->aggs[a].nf >= 1)
+            emitf(o, "          if (!(__builtin_fabs(va%d) <= 1.7976931348623157e308)) {\n"
+                     "            if (ok) atomicAdd(&bacc[slot * %d + %d], va%d);\n"
+                     "            va%d = 0.0;\n"
+                     "          }\n", a, s.NA1, a, a, a);
+        o += "        }\n";
+      }
+      for (int a = 0; a < s.NA; a++)
+        if (g.p->aggs[a].op != 0)
+          emitf(o, "        const u64 vo%d = f64ordc(va%d);\n", a, a);
       emitf(o, "#pragma unroll\n        for (int s = 0; s < %d; s++) {\n"
-               "          const double m = (ok && slot == s) ? 1.0 : 0.0;\n"
+               "          const bool mine = ok && slot == s;\n"
+               "          const double m = mine ? 1.0 : 0.0;\n"
                "          rc[s] += m;\n", s.NS);
       for (int a = 0; a < s.NA; a++) {
         const int op = g.p->aggs[a].op;
@@ -1004,13 +1071,12 @@ static void emit_accumulate(Gen &g) {
           emitf(o, "          sums[s][%d] = __builtin_fma(m, va%d, sums[s][%d]);\n",
                 a, a, a);
         else
-          emitf(o, "          sums[s][%d] = %s(sums[s][%d],\n"
-                   "              (ok && slot == s) ? va%d : __longlong_as_double(%s));\n",
-                a, op == 1 ? "fmin" : "fmax", a, a,
-                op == 1 ? "0x7FF0000000000000ll" : "0xFFF0000000000000ll");
+          emitf(o, "          if (mine && vo%d %s ords[s][%d]) ords[s][%d] = vo%d;\n",
+                a, op == 1 ? "<" : ">", a, a, a);
       }
       o += "        }\n";
       break;
+    }
     case ACC_KEYLESS:
       for (int a = 0; a < s.NA; a++) {
         emitf(o, "        sums[%d] += ok ? va%d : 0.0;\n", a, a);
@@ -1073,8 +1139,7 @@ static void emit_flush(Gen &g) {
                "  }\n", s.nv, s.nv);
       break;
     case ACC_REGS:
-      /* block reduce into LDS bacc then scratch row */
-      emit_acc_init(o, g, "bacc", s.nv, s.mm_any);
+      /* block reduce into LDS bacc (zeroed at entry) then scratch row */
       emitf(o, "#pragma unroll\n  for (int s = 0; s < %d; s++) {\n", s.NS);
       for (int a = 0; a < s.NA; a++) {
         const int op = g.p->aggs[a].op;
@@ -1083,10 +1148,10 @@ static void emit_flush(Gen &g) {
                    "      if ((tid & 63) == 0 && x != 0.0) atomicAdd(&bacc[s * %d + %d], x); }\n",
                 a, s.NA1, a);
         else
-          emitf(o, "    { double x = %s(sums[s][%d]);\n"
+          emitf(o, "    { const u64 x = %s(ords[s][%d]);\n"
                    "      if ((tid & 63) == 0)\n"
-                   "        %s((unsigned long long *)&bacc[s * %d + %d], f64ord(x)); }\n",
-                op == 1 ? "wmin" : "wmax", a,
+                   "        %s((unsigned long long *)&bacc[s * %d + %d], x); }\n",
+                op == 1 ? "wminu" : "wmaxu", a,
                 op == 1 ? "atomicMin" : "atomicMax", s.NA1, a);
       }
       emitf(o, "    { double x = wsum(rc[s]);\n"
@@ -1140,6 +1205,7 @@ static std::string gen_source(const sn_dev_plan *p, const int *kinds,
             offsetof(sn_dev_col, rle_vals));
       break;
     }
+  emit_order_helpers(g);
   emit_signature(g);
   emit_literals(g);
   emit_acc_decl(g);

@@ -310,13 +310,11 @@ __device__ __forceinline__ void convert_chunk(
       if ((tid & 63) == 0) sdead[r >> 6] = w;
     }
   }
-  /* short chunks MUST zero the image tail: sval beyond `rows` is raw LDS
-   * left by whatever kernel ran last on this CU.  Dead rows never
-   * contribute through selects, but the slot-predicated fma accumulators
-   * compute fma(0, va, sum) — and fma(0, NaN, s) = NaN, so an ord-ident
-   * bit pattern (0xFFF8...) parked in LDS silently poisons every sum in
-   * the wave (found by the randomized parity fuzzer as a
-   * prior-query-dependent NaN). */
+  /* short chunks zero the image tail: sval beyond `rows` is raw LDS left by
+   * whatever kernel ran last on this CU.  Every accumulator selects a dead
+   * row's value away, so this is no longer what keeps a parked NaN pattern
+   * (0xFFF8...) out of the sums; it keeps the values that the row phase
+   * computes on defined. */
   if (rows < CHUNK) {
     for (int c = 0; c < nused; c++) {
       double *dst = sval + (size_t)c * CHUNK;
@@ -557,6 +555,14 @@ __device__ __forceinline__ unsigned long long f64_ord(double x) {
 }
 #define ORD_MIN_IDENT 0xFFF8000000000000ull   /* enc(+inf) < this; safe top */
 #define ORD_MAX_IDENT 0x0000000000000000ull   /* below enc(-inf) */
+/* the aggregates' ordering (non-finite aggregate inputs): every
+ * NaN, whatever its sign and payload, is one value above +inf.  Its image is
+ * that of the positive quiet NaN, which is also MIN's identity: a group of
+ * NaNs alone leaves the cell there and decodes to NaN, its count says it is
+ * not NULL. */
+__device__ __forceinline__ unsigned long long f64_ord_agg(double x) {
+  return x != x ? ORD_MIN_IDENT : f64_ord(x);
+}
 
 /* op-aware accumulate into an accumulator cell (LDS or global).
  * Sum cells hold plain doubles; min/max cells hold the ord-u64 encoding
@@ -566,9 +572,9 @@ __device__ __forceinline__ void acc_cell(PTR *cell, int op, double va) {
   if (op == 0) {
     (void)atomicAdd((double *)cell, va);
   } else if (op == 1) {
-    (void)atomicMin((unsigned long long *)cell, f64_ord(va));
+    (void)atomicMin((unsigned long long *)cell, f64_ord_agg(va));
   } else {
-    (void)atomicMax((unsigned long long *)cell, f64_ord(va));
+    (void)atomicMax((unsigned long long *)cell, f64_ord_agg(va));
   }
 }
 
@@ -1186,11 +1192,13 @@ __global__ void k_grouped(sn_dev_plan plan,
           const double vb = eval_agg(P, B2, sval, r);
 #pragma unroll
           for (int s = 0; s < NSLOTS; s++) {
-            /* fma(md, x, acc) is bit-identical to the select+add form and
-             * halves the VALU ops per slot */
-            const double md = (m && slot == s) ? 1.0 : 0.0;
-            sa[s] = __builtin_fma(md, va, sa[s]);
-            sb[s] = __builtin_fma(md, vb, sb[s]);
+            /* select + add: a row adds to its own slot alone and a dead row
+             * to none.  (fma(0 or 1, x, acc) is one op less, but
+             * fma(0, +-inf or NaN, acc) is NaN: one such value, of a
+             * filtered row included, turned every slot of the lane NaN.) */
+            const bool mine = m && slot == s;
+            sa[s] += mine ? va : 0.0;
+            sb[s] += mine ? vb : 0.0;
           }
         }
 #pragma unroll
@@ -1353,11 +1361,12 @@ __global__ void k_grouped_reg(sn_dev_plan plan,
         }
 #pragma unroll
         for (int s = 0; s < NSLOTS; s++) {
-          const double md = (m && slot == s) ? 1.0 : 0.0;
-          rc[s] += md;
+          /* select + add, not fma(0 or 1, va, sum): see k_grouped */
+          const bool mine = m && slot == s;
+          rc[s] += mine ? 1.0 : 0.0;
 #pragma unroll
           for (int a = 0; a < NA; a++)
-            sums[s][a] = __builtin_fma(md, va[a], sums[s][a]);
+            sums[s][a] += mine ? va[a] : 0.0;
         }
       }
   });
