@@ -361,6 +361,13 @@ int32_t   sn_query_result_page(sn_query *q, int64_t offset, sn_result *out);
 int64_t   sn_query_num_groups(sn_query *q);
 /* 1 when the query ran a query-compiled (hipRTC) kernel, 0 interpreted */
 int32_t   sn_query_used_jit(sn_query *q);
+/* bit c set: the compiled kernel read table column c "late", that is for the
+ * rows that pass the predicates only, instead of streaming it whole.  The
+ * engine does this for plain DOUBLE columns that only aggregate factors use,
+ * in keyless plans whose predicates are estimated (from the batch bounds)
+ * to keep few rows.  0 when no column was, SN_LATE=0 was set when the
+ * engine was created, or the query ran interpreted.  Columns 0..62. */
+int64_t   sn_query_late_cols(sn_query *q);
 /* ORDER BY <aggregate value> [DESC] LIMIT k epilogue (SnappySortExec /
  * TakeOrderedAndProject semantics, core/.../SnappySortExec.scala): reorders
  * the finalized group rows by aggregate `agg_idx`'s value (NULLs last,

@@ -300,6 +300,12 @@ struct sn_engine {
   /* SN_NARROW (default on, 0 = off), read once per engine: narrow
    * low-cardinality f64 columns into 1-byte code sidecars at put */
   bool narrow = true;
+  /* SN_LATE (default on, 0 = off), read once per engine: a keyless compiled
+   * scan reads its aggregate-only f64 columns for the passing rows alone
+   * when the predicates are estimated to keep at most SN_LATE_MAX_SEL of the
+   * rows.  SN_LATE=force engages whatever the estimate
+   * (measurement only). */
+  bool late = true, late_force = false;
   /* reusable per-engine scratch for block-partial reduction rows
    * (queries on one engine serialize on its stream) */
   double *scratch = nullptr;
@@ -376,6 +382,10 @@ extern "C" sn_engine *sn_engine_create(const sn_config *cfg) {
   if (e->cfg.shard_count <= 0) e->cfg.shard_count = 1;
   if (e->cfg.n_buckets <= 0) e->cfg.n_buckets = 128;
   if (const char *nv = getenv("SN_NARROW")) e->narrow = nv[0] != '0';
+  if (const char *lv = getenv("SN_LATE")) {
+    e->late = lv[0] != '0';
+    e->late_force = !strcmp(lv, "force");
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && e->cfg.device >= 0) {
     if (hipSetDevice(e->cfg.device) == hipSuccess &&
@@ -2052,6 +2062,7 @@ struct sn_query {
   std::vector<std::pair<void *, size_t>> owned;
   float kernel_ms = -1.0f;
   bool used_jit = false;                /* query-compiled kernel ran */
+  int64_t late_cols = 0;                /* table columns it read late (bit c) */
   bool done = false;
   bool merged = false;
   std::vector<GroupOut> final_groups;
@@ -3095,6 +3106,83 @@ static void *cached_dev_plan(sn_engine *e, const sn_dev_plan &dp) {
   return dp_dev;
 }
 
+/* ---- late columns ----
+ * The fraction of rows the plan's predicates keep, estimated from what the
+ * batch-skip test already holds: each range predicate is taken as uniform
+ * over [min, max] of its column across the unskipped batches (value counts
+ * for integer columns, widths for doubles), and the fractions multiply.
+ * String-equality and IN-list predicates count as keeping everything.  A
+ * predicate column without bounds in some batch, or a batch with update
+ * deltas (its bounds do not cover them), means no estimate: 1.0. */
+#define SN_LATE_MAX_SEL 0.05
+
+static double estimate_selectivity(const sn_query *q) {
+  const Table *t = q->t;
+  const sn_plan *p = &q->plan;
+  double sel = 1.0;
+  for (int i = 0; i < p->npreds; i++) {
+    const sn_pred &pr = p->preds[i];
+    if (pr.in_n > 0 || pr.str_eq || (!pr.has_lo && !pr.has_hi)) continue;
+    const int c = pr.col;
+    const sn_type_t dt = t->schema[c].dtype;
+    const bool is_d = dt == SN_TYPE_DOUBLE || dt == SN_TYPE_FLOAT;
+    bool any = false;
+    double cmin = 0, cmax = 0;
+    for (auto &b : t->batches) {
+      if (q->batches_skipped && batch_skippable(b, p, t)) continue;
+      if (!b.stats_valid || b.has_deltas || b.bounds_null[c]) return 1.0;
+      const double lo = is_d ? b.lo_d[c] : (double)b.lo_i[c];
+      const double hi = is_d ? b.hi_d[c] : (double)b.hi_i[c];
+      cmin = any ? std::min(cmin, lo) : lo;
+      cmax = any ? std::max(cmax, hi) : hi;
+      any = true;
+    }
+    if (!any || !(cmax >= cmin)) return 1.0;   /* no batch, or NaN bounds */
+    /* integer columns count values: [lo, hi] closed after the strict bits */
+    const double unit = is_d ? 0.0 : 1.0;
+    double lo = cmin, hi = cmax;
+    if (pr.has_lo) lo = std::max(lo, is_d ? pr.lo_d : (double)pr.lo_i + (pr.lo_strict ? 1 : 0));
+    if (pr.has_hi) hi = std::min(hi, is_d ? pr.hi_d : (double)pr.hi_i - (pr.hi_strict ? 1 : 0));
+    const double span = cmax - cmin + unit, kept = hi - lo + unit;
+    if (!(kept > 0.0)) return 0.0;
+    if (span > 0.0) sel *= std::min(1.0, kept / span);
+  }
+  return sel;
+}
+
+/* Which used columns the compiled kernel of this launch reads late: plain
+ * f64 columns (SN_K_F64 in every unskipped batch; the set is JIT-eligible,
+ * so no nulls and no patches) that aggregate factors use and nothing else
+ * does, in a keyless plan whose predicates are estimated to keep at most
+ * SN_LATE_MAX_SEL of the rows.  kinds[] is the launch's copy of the set's
+ * kinds; the device descriptors keep SN_K_F64.  Returns the used-slot mask. */
+static uint32_t tag_late_columns(const sn_query *q, const sn_dev_plan &dp,
+                                 int *kinds) {
+  const sn_engine *e = q->e;
+  const sn_plan *plan = &q->plan;
+  if (!e->late || plan->ngroup > 0 || q->join_dim || q->sparse || dp.nslots > 1)
+    return 0;
+  uint32_t agg = 0, other = 0;
+  for (int a = 0; a < dp.naggs; a++) {
+    const sn_dev_agg &A = dp.aggs[a];
+    if (A.nf >= 1) agg |= 1u << A.c0;
+    if (A.nf >= 2) agg |= 1u << A.c1;
+    if (A.nf >= 3) agg |= 1u << A.c2;
+  }
+  for (int i = 0; i < dp.npreds_d; i++) other |= 1u << dp.preds_d[i].cslot;
+  for (int i = 0; i < dp.npreds_i; i++) other |= 1u << dp.preds_i[i].cslot;
+  for (int i = 0; i < dp.npreds_in && i < 2; i++) other |= 1u << dp.inp[i].cslot;
+  uint32_t mask = 0;
+  for (int ui = 0; ui < dp.nused; ui++)
+    if (kinds[ui] == SN_K_F64 && ((agg & ~other) >> ui & 1)) mask |= 1u << ui;
+  /* some staged column must remain to carry the predicates */
+  if (!mask || !other) return 0;
+  if (!e->late_force && !(estimate_selectivity(q) <= SN_LATE_MAX_SEL)) return 0;
+  for (int ui = 0; ui < dp.nused; ui++)
+    if ((mask >> ui) & 1) kinds[ui] = SN_K_F64_LATE;
+  return mask;
+}
+
 /* ---- dense launch: keyless or direct-slot grouped (k_scan_agg family or
  * its query-compiled twin) into a per-query result buffer ---- */
 static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
@@ -3131,8 +3219,19 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
   void *jfn = nullptr;
   /* pac from ACTUAL nulls never reaches here (jit_ok excludes null
    * batches); pac from MIN/MAX compiles op-aware kernels. */
-  if (e->jit && sn_jit_shape_ok(&dp) && jit_inlists_ok(dp) && set.jit_ok)
-    jfn = sn_jit_get(e->jit, &dp, set.jit_kinds, dp.nslots, q->na_t, set.jit_del);
+  uint32_t late = 0;
+  if (e->jit && sn_jit_shape_ok(&dp) && jit_inlists_ok(dp) && set.jit_ok) {
+    /* the late tag depends on this plan's predicate bounds, which the cached
+     * set's signature leaves out: it goes on a copy of the set's kinds */
+    int kinds[SN_DEV_MAX_COLS];
+    memcpy(kinds, set.jit_kinds, sizeof(kinds));
+    late = tag_late_columns(q, dp, kinds);
+    jfn = sn_jit_get(e->jit, &dp, kinds, dp.nslots, q->na_t, set.jit_del);
+  }
+  if (jfn)
+    for (size_t ui = 0; ui < q->used_cols.size(); ui++)
+      if (((late >> ui) & 1) && q->used_cols[ui] < 63)
+        q->late_cols |= 1ll << q->used_cols[ui];
   if (q->ev_start) (void)hipEventRecord(q->ev_start, e->stream);
   rc = -1;
   if (jfn) {
@@ -3535,6 +3634,12 @@ extern "C" double sn_query_kernel_ms(sn_query *q) {
 /* 1 when the query ran a query-compiled (hipRTC) kernel, 0 interpreted */
 extern "C" int32_t sn_query_used_jit(sn_query *q) {
   return q && q->used_jit ? 1 : 0;
+}
+
+/* bit c set: the compiled kernel of this query read table column c late,
+ * for the passing rows only (columns 0..62; 0 when none, or interpreted) */
+extern "C" int64_t sn_query_late_cols(sn_query *q) {
+  return q && q->used_jit ? q->late_cols : 0;
 }
 
 /* number of compiled kernels in this engine's JIT cache (tokenized plan

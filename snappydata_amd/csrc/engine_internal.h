@@ -42,10 +42,16 @@ enum {
                         the host materializes their values into a plain
                         fixed-width body at put — decompress-on-put, like
                         the LZ4 wrapper.) */
-  SN_K_F64C8 = 12    /* narrowed double: body = 1-byte codes (the put-time
+  SN_K_F64C8 = 12,   /* narrowed double: body = 1-byte codes (the put-time
                         sidecar, not the blob), rle_vals = the batch's value
                         dictionary of rle_n <= 256 doubles, value =
                         rle_vals[body[row]] — bit for bit the f64 body's */
+  SN_K_F64_LATE = 13 /* JIT-only, never in a device descriptor (which keeps
+                        SN_K_F64 and the same body): a double column that only
+                        aggregate factors use, in a keyless plan whose
+                        predicates keep few rows.  The compiled kernel does
+                        not stage it; it reads it in the row phase, for the
+                        rows that pass alone. */
 };
 
 typedef struct {

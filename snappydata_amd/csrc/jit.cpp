@@ -125,6 +125,11 @@ struct JitShape {
   JitSlot slot;
   long long slut_span, slut_words;
   int occupancy;     /* second __launch_bounds__ argument */
+  int nlate;         /* late columns: read in the row phase, passing rows only */
+  int nstaged;       /* staged columns = rows of the LDS image */
+  int lds_dict;      /* value dictionaries are looked up in an LDS copy */
+  int late[SN_DEV_MAX_COLS];   /* column is late */
+  int srow[SN_DEV_MAX_COLS];   /* a staged column's row of the LDS image */
 };
 
 /* pac: per-agg-count accumulator rows ([sums][counts][rowcount]).  In
@@ -186,7 +191,7 @@ extern "C" int sn_jit_shape_ok(const sn_dev_plan *p) {
 
 static JitShape jit_classify(const sn_dev_plan *p, const int *kinds,
                              int nslots, int na_t, int has_del) {
-  (void)kinds; (void)has_del;
+  (void)has_del;
   JitShape s;
   s.NC = p->nused;
   s.NA = p->naggs;
@@ -232,6 +237,39 @@ static JitShape jit_classify(const sn_dev_plan *p, const int *kinds,
   if (sparse) s.occupancy = spocc_env > 0 ? spocc_env : 4;
   else if (s.acc == ACC_LDS || s.acc == ACC_GLOBAL) s.occupancy = 1;
   else s.occupancy = s.acc == ACC_WBIN ? 4 : 2;
+
+  /* Late columns (SN_K_F64_LATE): honoured where the engine tags them, in
+   * the keyless register modes without a probe; anywhere else, and when no
+   * staged column would be left to carry the predicates, the column is
+   * staged like the SN_K_F64 its descriptor says it is.  So is a column
+   * that a predicate reads: predicates run on the image. */
+  const bool late_mode = s.probe == PROBE_NONE &&
+      (s.acc == ACC_KEYLESS || (s.acc == ACC_REGS && s.slot == SLOT_SINGLE));
+  unsigned pred_cols = 0;
+  for (int i = 0; i < p->npreds_d; i++) pred_cols |= 1u << p->preds_d[i].cslot;
+  for (int i = 0; i < p->npreds_i; i++) pred_cols |= 1u << p->preds_i[i].cslot;
+  for (int i = 0; i < p->npreds_in && i < 2; i++)
+    pred_cols |= 1u << p->inp[i].cslot;
+  s.nlate = 0;
+  for (int c = 0; c < s.NC; c++)
+    s.nlate += s.late[c] = late_mode && kinds[c] == SN_K_F64_LATE &&
+                           !((pred_cols >> c) & 1);
+  if (s.nlate == s.NC) {
+    s.nlate = 0;
+    for (int c = 0; c < s.NC; c++) s.late[c] = 0;
+  }
+  s.nstaged = 0;
+  for (int c = 0; c < s.NC; c++) s.srow[c] = s.late[c] ? -1 : s.nstaged++;
+  /* A kernel with a late column copies each value dictionary (256 doubles,
+   * one per lane) into LDS once per tile and converts the staged codes from
+   * there: two 8-byte gathers per row through the vector L1 are what bounds
+   * the all-staged Q6 kernel (profiles/README.md, r04), not its HBM bytes.
+   * SN_JIT_LATE_LDSDICT=0 keeps the global lookups, for A/B runs. */
+  static const int lds_dict_env = [] {
+    const char *v = getenv("SN_JIT_LATE_LDSDICT");
+    return !v || v[0] != '0';
+  }();
+  s.lds_dict = s.nlate > 0 && lds_dict_env;
   return s;
 }
 
@@ -270,7 +308,7 @@ static const JitKind &jit_kind(int k) {
   static const JitKind c8 = { "unsigned short", 1, "unsigned char", CV_VDICT,
                               0, 0 };
   switch (k) {
-    case SN_K_F64: return f64;
+    case SN_K_F64: case SN_K_F64_LATE: return f64;
     case SN_K_I64: return i64;
     case SN_K_I32: return i32;
     case SN_K_F32: return f32;
@@ -552,7 +590,11 @@ static void emit_acc_init(std::string &o, const Gen &g, const char *acc,
 static void emit_acc_decl(Gen &g) {
   std::string &o = g.o;
   const JitShape &s = g.s;
-  emitf(o, "  __shared__ __attribute__((aligned(16))) double sval[%d][CHUNK];\n", s.NC);
+  emitf(o, "  __shared__ __attribute__((aligned(16))) double sval[%d][CHUNK];\n", s.nstaged);
+  static_assert(JIT_WG == SN_NARROW_MAX, "one dictionary entry per lane");
+  for (int c = 0; c < s.NC && s.lds_dict; c++)
+    if (jit_kind(g.kinds[c]).conv == CV_VDICT)
+      emitf(o, "  __shared__ __attribute__((aligned(16))) double svd%d[WG];\n", c);
   /* shared arrays precede tid in the text; the rest of each mode follows */
   std::string d;
   const char *bacc = "  __shared__ __attribute__((aligned(16))) double bacc[%d];\n";
@@ -642,7 +684,8 @@ static void emit_probe_decl(Gen &g) {
 /* staged register buffers: per column, by width class */
 static void emit_stage_regs(Gen &g) {
   for (int c = 0; c < g.s.NC; c++)
-    emitf(g.o, "  %s st%d_0, st%d_1;\n", jit_kind(g.kinds[c]).reg, c, c);
+    if (!g.s.late[c])
+      emitf(g.o, "  %s st%d_0, st%d_1;\n", jit_kind(g.kinds[c]).reg, c, c);
 }
 
 /* pack the dense LUT into 4-bit LDS nibbles, once per workgroup:
@@ -683,11 +726,23 @@ static void emit_tile_prologue(Gen &g) {
     if (jit_kind(g.kinds[c]).conv == CV_VDICT)
       emitf(o, "    const GAS double *vd%d = (const GAS double *)(unsigned long long)b.cols[%d].rle_vals;\n", c, c);
   }
+  if (!g.s.lds_dict) return;
+  /* the batch's dictionaries into LDS (a sidecar always holds 256 entries).
+   * The last reads of the previous tile's copy are behind the barrier that
+   * ends its chunk loop; this one orders the copy before stage_write. */
+  bool any = false;
+  for (int c = 0; c < g.s.NC; c++)
+    if (jit_kind(g.kinds[c]).conv == CV_VDICT) {
+      emitf(o, "    svd%d[tid] = vd%d[tid];\n", c, c);
+      any = true;
+    }
+  if (any) o += "    __syncthreads();\n";
 }
 
 /* stage_load body, emitted in the prologue and inside the chunk loop */
 static void emit_stage_load(Gen &g, const char *base_expr, const char *ind) {
   for (int c = 0; c < g.s.NC; c++) {
+    if (g.s.late[c]) continue;
     const JitKind &K = jit_kind(g.kinds[c]);
     emitf(g.o, "%sst%d_0 = ((const GAS %s *)(body%d + (u64)(%s) * %d))[tid];\n",
           ind, c, K.reg, c, base_expr, K.bytes);
@@ -700,10 +755,12 @@ static void emit_stage_load(Gen &g, const char *base_expr, const char *ind) {
 static void emit_stage_write(Gen &g, const char *ind) {
   std::string &o = g.o;
   for (int c = 0; c < g.s.NC; c++) {
+    if (g.s.late[c]) continue;
     const JitKind &K = jit_kind(g.kinds[c]);
+    const int sr = g.s.srow[c];
     if (K.conv == CV_BITS64) {
-      emitf(o, "%s((double2_t *)sval[%d])[tid] = st%d_0;\n", ind, c, c);
-      emitf(o, "%s((double2_t *)sval[%d])[tid + WG] = st%d_1;\n", ind, c, c);
+      emitf(o, "%s((double2_t *)sval[%d])[tid] = st%d_0;\n", ind, sr, c);
+      emitf(o, "%s((double2_t *)sval[%d])[tid + WG] = st%d_1;\n", ind, sr, c);
       continue;
     }
     std::string y[2], st[2];
@@ -711,8 +768,13 @@ static void emit_stage_write(Gen &g, const char *ind) {
       y[h] = strf("double2_t y%d; y%d.x = %s; y%d.y = %s;", h, h,
                   kind_image_from_reg(K, c, 2 * h).c_str(), h,
                   kind_image_from_reg(K, c, 2 * h + 1).c_str());
-      st[h] = strf("((double2_t *)sval[%d])[tid%s] = y%d;", c,
+      st[h] = strf("((double2_t *)sval[%d])[tid%s] = y%d;", sr,
                    h ? " + WG" : "", h);
+      if (g.s.lds_dict && K.conv == CV_VDICT) {   /* vd<c>[..] -> svd<c>[..] */
+        const std::string gl = strf(" vd%d[", c);
+        for (size_t at; (at = y[h].find(gl)) != std::string::npos;)
+          y[h].replace(at, gl.size(), strf(" svd%d[", c));
+      }
     }
     emitf(o, "%s{ ", ind);
     if (K.conv == CV_F32)
@@ -735,11 +797,13 @@ static void emit_scalar_tail(Gen &g) {
        "         * previous kernel, and fma(0, NaN, sum) = NaN would poison\n"
        "         * the slot-predicated register accumulators) */\n";
   for (int c = 0; c < g.s.NC; c++)
-    emitf(o, "        for (int r = tid; r < rows; r += WG) sval[%d][r] = %s;\n",
-          c, kind_image_from_mem(jit_kind(g.kinds[c]), c).c_str());
+    if (!g.s.late[c])
+      emitf(o, "        for (int r = tid; r < rows; r += WG) sval[%d][r] = %s;\n",
+            g.s.srow[c], kind_image_from_mem(jit_kind(g.kinds[c]), c).c_str());
   for (int c = 0; c < g.s.NC; c++)
-    emitf(o, "        for (int r = rows + tid; r < CHUNK; r += WG)"
-             " sval[%d][r] = 0.0;\n", c);
+    if (!g.s.late[c])
+      emitf(o, "        for (int r = rows + tid; r < CHUNK; r += WG)"
+               " sval[%d][r] = 0.0;\n", g.s.srow[c]);
 }
 
 /* one dense-LUT lookup: dst = payload of kexpr, or -1 outside the span */
@@ -814,12 +878,12 @@ static void emit_row_predicates(Gen &g) {
   for (int i = 0; i < p->npreds_d; i++) {
     emitf(o, "        { const double x = sval[%d][r];\n"
              "          ok &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n",
-          p->preds_d[i].cslot, i, i);
+          g.s.srow[p->preds_d[i].cslot], i, i);
   }
   for (int i = 0; i < p->npreds_i; i++) {
     emitf(o, "        { const i64 x = __double_as_longlong(sval[%d][r]);\n"
              "          ok &= (x >= pi%d_lo) & (x <= pi%d_hi); }\n",
-          p->preds_i[i].cslot, i, i);
+          g.s.srow[p->preds_i[i].cslot], i, i);
   }
   for (int i = 0; i < p->npreds_in && i < 2; i++) {
     const int cs = p->inp[i].cslot;
@@ -828,9 +892,40 @@ static void emit_row_predicates(Gen &g) {
              "          const i64 ix = v - inb%d_base;\n"
              "          ok &= (ix >= 0) & (ix < inb%d_lim) &\n"
              "                (int)((inbm%d[ix >> 6] >> (ix & 63)) & 1ull); }\n",
-          is64 ? "__double_as_longlong(" : "(i64)", cs, is64 ? ")" : "",
-          i, i, i);
+          is64 ? "__double_as_longlong(" : "(i64)", g.s.srow[cs],
+          is64 ? ")" : "", i, i, i);
   }
+}
+
+/* Late columns: the row phase runs as two fully unrolled passes, so the
+ * arrays below stay in registers.  Pass A forms every slot's `ok` from the
+ * image of the staged columns and issues the late loads of the chunk, each
+ * under its row's `ok`: `ok` holds r < rows and the delete bit, so no lane
+ * reads past num_rows; a 128-byte line of the column in which no row passes
+ * is not requested; and a row that does not pass is never read, whatever it
+ * holds.  Pass B consumes them in ascending k, the order of the one-pass
+ * row phase. */
+static void emit_late_stash(Gen &g) {
+  g.o += "      int okv[CHUNK / WG];\n";
+  for (int c = 0; c < g.s.NC; c++)
+    if (g.s.late[c]) emitf(g.o, "      double e%d[CHUNK / WG];\n", c);
+}
+
+/* end of pass A, head of pass B */
+static void emit_late_split(Gen &g) {
+  std::string &o = g.o;
+  o += "        okv[k] = ok;\n";
+  for (int c = 0; c < g.s.NC; c++)
+    if (g.s.late[c])
+      emitf(o, "        e%d[k] = 0.0;\n"
+               "        if (ok) e%d[k] = ((const GAS double *)(body%d))[base + r];\n",
+            c, c, c);
+  o += "      }\n"
+       "#pragma unroll\n"
+       "      for (int k = 0; k < CHUNK / WG; k++) {\n"
+       "        const int r = tid + k * WG;\n"
+       "        const int ok = okv[k];\n"
+       "        (void)r;\n";
 }
 
 /* broadcast-dimension probe with literal table shape (mask, key slot,
@@ -977,9 +1072,10 @@ static void emit_agg_values(Gen &g) {
   /* factor read: i64 slots hold raw bits in the LDS image — emit the
    * convert only for those slots (compile-time; i64_mask is in the shape) */
   auto factor = [&](int a, int i, int cs, double fa, double fm) {
-    const std::string f = plan_col_is_i64(g.p, cs)
-        ? strf("(double)__double_as_longlong(sval[%d][r])", cs)
-        : strf("sval[%d][r]", cs);
+    const std::string f = g.s.late[cs] ? strf("e%d[k]", cs)
+        : plan_col_is_i64(g.p, cs)
+        ? strf("(double)__double_as_longlong(sval[%d][r])", g.s.srow[cs])
+        : strf("sval[%d][r]", g.s.srow[cs]);
     if (ftriv(fa, fm)) return f;
     return strf("__builtin_fma(ag%d_m%d, %s, ag%d_a%d)", a, i, f.c_str(), a, i);
   };
@@ -1240,13 +1336,15 @@ static std::string gen_source(const sn_dev_plan *p, const int *kinds,
 
   /* row pass: predicates, probe, slot, values and accumulate in one sweep */
   if (radix) emit_radix_stash(g);
-  o += radix ? "#pragma unroll\n" : "#pragma unroll 2\n";
+  if (g.s.nlate) emit_late_stash(g);
+  o += radix || g.s.nlate ? "#pragma unroll\n" : "#pragma unroll 2\n";
   o += "      for (int k = 0; k < CHUNK / WG; k++) {\n"
        "        const int r = tid + k * WG;\n"
        "        int ok = r < rows;\n";
   emit_row_predicates(g);
   if (radix)   /* before the wave skip: pass B keys off rok alone */
     o += "        rok[k] = ok;\n";
+  if (g.s.nlate) emit_late_split(g);
   o += "        if (__popcll(__ballot(ok)) == 0) continue;\n";
   emit_join_probe(g);
   emit_slot(g);

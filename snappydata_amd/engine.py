@@ -92,6 +92,8 @@ def lib():
         L.sn_query_kernel_ms.argtypes = [C.c_void_p]
         L.sn_query_used_jit.restype = C.c_int32
         L.sn_query_used_jit.argtypes = [C.c_void_p]
+        L.sn_query_late_cols.restype = C.c_int64
+        L.sn_query_late_cols.argtypes = [C.c_void_p]
         L.sn_query_order_by.restype = C.c_int32
         L.sn_query_order_by.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int64]
@@ -333,6 +335,14 @@ class Query:
     def used_jit(self):
         """True when the query ran a query-compiled (hipRTC) kernel."""
         return bool(lib().sn_query_used_jit(self._h))
+
+    def late_cols(self):
+        """Table columns the compiled kernel read for the passing rows only
+        (aggregate-only DOUBLE columns of a selective keyless plan); empty
+        when none were, or with SN_LATE=0 in the environment when the engine
+        was created."""
+        m = int(lib().sn_query_late_cols(self._h))
+        return [c for c in range(63) if (m >> c) & 1]
 
     def order_by(self, agg_idx, descending=False, k=0):
         """ORDER BY <aggregate value> [DESC] LIMIT k epilogue
