@@ -26,6 +26,7 @@
 #include <cstdio>
 
 #include "../../include/snappy_engine.h"
+#include "engine_internal.h"
 
 extern "C" int32_t sn_batch_put(sn_engine *, int32_t, int64_t, int32_t, int32_t,
                                 const sn_buf *, const sn_buf *, const sn_buf *,
@@ -94,14 +95,8 @@ static int encode_column(sn_type_t dtype, const sn_ingest_col &col,
     return SN_OK;
   }
   put_header(out, SN_ENC_UNCOMPRESSED, valid, count);
-  int w;
-  switch (dtype) {
-    case SN_TYPE_DOUBLE: case SN_TYPE_INT64: w = 8; break;
-    case SN_TYPE_INT32: case SN_TYPE_FLOAT: w = 4; break;
-    case SN_TYPE_INT16: w = 2; break;
-    case SN_TYPE_INT8: case SN_TYPE_BOOL: w = 1; break;
-    default: return SN_ERR_UNSUPPORTED;
-  }
+  const int w = sn_type_width(dtype);
+  if (w == 0) return SN_ERR_UNSUPPORTED;
   if (!valid) {
     out.insert(out.end(), v8, v8 + (size_t)count * w);
   } else {
@@ -180,9 +175,7 @@ extern "C" int64_t sn_ingest_columns(sn_engine *e, int32_t table, int64_t nrows,
         for (int32_t i = 0; i < n; i++) bytes += cols[c].str_lens[s + i];
         str_off[c] += bytes;
       } else {
-        int w = (ti.dtypes[c] == SN_TYPE_DOUBLE || ti.dtypes[c] == SN_TYPE_INT64) ? 8 :
-                (ti.dtypes[c] == SN_TYPE_INT16) ? 2 :
-                (ti.dtypes[c] == SN_TYPE_INT8 || ti.dtypes[c] == SN_TYPE_BOOL) ? 1 : 4;
+        const int w = sn_type_width(ti.dtypes[c]);
         view.data = base + (int64_t)s * w;
         bool rawable = !view.valid &&
             (ti.dtypes[c] == SN_TYPE_DOUBLE || ti.dtypes[c] == SN_TYPE_FLOAT ||

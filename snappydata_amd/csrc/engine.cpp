@@ -52,6 +52,7 @@
 
 #include "../../include/snappy_engine.h"
 #include "engine_internal.h"
+#include "blob_format.h"
 
 /* ------------------------------------------------------------------ */
 /* error reporting                                                     */
@@ -70,14 +71,6 @@ extern "C" const char *sn_engine_arch(void) { return "gfx950"; }
 
 #define HIP_OR_FAIL(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
   return fail(SN_ERR_GENERIC, "%s failed: %s", #x, hipGetErrorString(e_)); } while (0)
-
-/* ------------------------------------------------------------------ */
-/* little-endian readers (host is LE)                                  */
-static inline int32_t rd_i32(const uint8_t *p) { int32_t v; memcpy(&v, p, 4); return v; }
-static inline int64_t rd_i64(const uint8_t *p) { int64_t v; memcpy(&v, p, 8); return v; }
-static inline double  rd_f64(const uint8_t *p) { double v; memcpy(&v, p, 8); return v; }
-static inline float   rd_f32(const uint8_t *p) { float v; memcpy(&v, p, 4); return v; }
-static inline int16_t rd_i16(const uint8_t *p) { int16_t v; memcpy(&v, p, 2); return v; }
 
 /* ------------------------------------------------------------------ */
 /* device memory arena: bump allocator over big HBM slabs, plus a
@@ -134,19 +127,6 @@ struct Arena {
     for (void *p : slabs) (void)hipFree(p);
     for (void *p : host_allocs) free(p);
   }
-};
-
-/* ------------------------------------------------------------------ */
-/* parsed column blob metadata (host view)                             */
-struct ColMeta {
-  int type_id = 0;               /* encoding */
-  int64_t body_off = 0;          /* offset of fixed-width body / index array */
-  int64_t null_off = 0;          /* offset of null words (0 if none) */
-  int32_t num_null_words = 0;
-  int32_t dict_n = 0;            /* dictionary entries (dict encodings) */
-  std::vector<std::string> dict; /* string dictionary values */
-  std::vector<int64_t> dict_i;   /* int dictionary values */
-  std::vector<int32_t> local2global;  /* per-batch dict idx -> table-global id */
 };
 
 /* host-merged update patch for one column of one batch */
@@ -530,6 +510,25 @@ static inline uint64_t mix64h(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+/* the kernel kind and byte width of an UNCOMPRESSED body of `dtype`; false
+ * for types with no fixed-width body.  Callers that take only the numeric
+ * types (raw ingest, patch materialization, RLE values) ask for width >= 2:
+ * the 1-byte types are BOOL and INT8. */
+static bool fixed_type(sn_type_t dtype, int *kind, int *width) {
+  switch (dtype) {
+    case SN_TYPE_DOUBLE: *kind = SN_K_F64; break;
+    case SN_TYPE_INT32:  *kind = SN_K_I32; break;
+    case SN_TYPE_INT64:  *kind = SN_K_I64; break;
+    case SN_TYPE_FLOAT:  *kind = SN_K_F32; break;
+    case SN_TYPE_INT16:  *kind = SN_K_I16; break;
+    case SN_TYPE_BOOL:   *kind = SN_K_U8; break;
+    case SN_TYPE_INT8:   *kind = SN_K_S8; break;
+    default: return false;
+  }
+  *width = sn_type_width(dtype);
+  return true;
+}
+
 /* device descriptor of column c of batch b: body/null pointers, encoding ->
  * SN_K_* kind, RLE aux, dictionary map, patch pointers.  The one place a new
  * encoding or kind is added — the query descriptor build and the join build
@@ -553,19 +552,12 @@ static int fill_dev_col(sn_engine *e, const Table *t, Batch &b, int c, int mul,
     *clean = false;
   }
   switch (m.type_id) {
-    case SN_ENC_UNCOMPRESSED:
-      switch (dt) {
-        case SN_TYPE_DOUBLE: dc.kind = SN_K_F64; break;
-        case SN_TYPE_INT32: dc.kind = SN_K_I32; break;
-        case SN_TYPE_INT64: dc.kind = SN_K_I64; break;
-        case SN_TYPE_FLOAT: dc.kind = SN_K_F32; break;
-        case SN_TYPE_INT16: dc.kind = SN_K_I16; break;
-        case SN_TYPE_BOOL: dc.kind = SN_K_U8; break;
-        case SN_TYPE_INT8: dc.kind = SN_K_S8; break;
-        default:
-          return fail(SN_ERR_UNSUPPORTED, "uncompressed %d on GPU path", (int)dt);
-      }
+    case SN_ENC_UNCOMPRESSED: {
+      int width;
+      if (!fixed_type(dt, &dc.kind, &width))
+        return fail(SN_ERR_UNSUPPORTED, "uncompressed %d on GPU path", (int)dt);
       break;
+    }
     case SN_ENC_RUNLENGTH:
       if (b.rle_n[c] <= 0 && b.num_rows > 0)
         return fail(SN_ERR_UNSUPPORTED, "RLE col %d has no run aux", c);
@@ -838,67 +830,6 @@ static lz4_decomp_fn get_lz4(void) {
 
 /* if blob is codec-wrapped, decompress into *out and return 1; 0 if plain;
  * negative = error */
-/* Raw Snappy block decompress (format_description.txt of google/snappy —
- * the raw block format snappy-java's Snappy.compress emits, which the
- * reference wraps as codec 2, CompressionCodecId.scala:31).  No libsnappy
- * ships in this image, so the decoder is implemented here: varint32
- * uncompressed length, then literal (tag&3==0) and copy (1/2/4-byte
- * offset) elements; copies may overlap and run byte-by-byte. */
-static int snappy_decompress(const uint8_t *src, int64_t slen,
-                             std::vector<uint8_t> *out) {
-  int64_t ip = 0;
-  uint32_t ulen = 0;
-  int shift = 0;
-  while (ip < slen) {
-    uint8_t b = src[ip++];
-    ulen |= (uint32_t)(b & 0x7f) << shift;
-    if (!(b & 0x80)) break;
-    shift += 7;
-    if (shift > 28) return -1;
-  }
-  out->resize(ulen);
-  uint8_t *dst = out->data();
-  uint32_t op = 0;
-  while (ip < slen) {
-    uint8_t tag = src[ip++];
-    if ((tag & 3) == 0) {                        /* literal */
-      uint32_t n = (uint32_t)(tag >> 2) + 1;
-      if (n > 60) {
-        int nb = (int)n - 60;
-        if (ip + nb > slen) return -1;
-        n = 0;
-        for (int i = 0; i < nb; i++) n |= (uint32_t)src[ip + i] << (8 * i);
-        n += 1;
-        ip += nb;
-      }
-      if (ip + n > slen || (uint64_t)op + n > ulen) return -1;
-      memcpy(dst + op, src + ip, n);
-      ip += n; op += n;
-    } else {                                     /* copy */
-      uint32_t n, off;
-      if ((tag & 3) == 1) {
-        if (ip >= slen) return -1;
-        n = ((uint32_t)(tag >> 2) & 7) + 4;
-        off = ((uint32_t)(tag >> 5) << 8) | src[ip++];
-      } else if ((tag & 3) == 2) {
-        if (ip + 2 > slen) return -1;
-        n = (uint32_t)(tag >> 2) + 1;
-        off = (uint32_t)src[ip] | ((uint32_t)src[ip + 1] << 8);
-        ip += 2;
-      } else {
-        if (ip + 4 > slen) return -1;
-        n = (uint32_t)(tag >> 2) + 1;
-        off = (uint32_t)src[ip] | ((uint32_t)src[ip + 1] << 8) |
-              ((uint32_t)src[ip + 2] << 16) | ((uint32_t)src[ip + 3] << 24);
-        ip += 4;
-      }
-      if (off == 0 || off > op || (uint64_t)op + n > ulen) return -1;
-      for (uint32_t i = 0; i < n; i++) { dst[op] = dst[op - off]; op++; }
-    }
-  }
-  return op == ulen ? 0 : -1;
-}
-
 static int maybe_decompress(const uint8_t *blob, int64_t len,
                             std::vector<uint8_t> *out) {
   if (len < 8) return 0;
@@ -923,164 +854,6 @@ static int maybe_decompress(const uint8_t *blob, int64_t len,
     return 1;
   }
   return fail(SN_ERR_UNSUPPORTED, "codec %d not supported", codec);
-}
-
-/* ---- blob header parse (PRODUCT-side restatement of
- *      ColumnEncoding.scala:37-53,764-832; DictionaryEncoding.scala:85-160) */
-static int parse_blob(const uint8_t *blob, int64_t len, sn_type_t dtype,
-                      ColMeta *m) {
-  if (!blob || len < 8) return SN_ERR_BADFORMAT;
-  m->type_id = rd_i32(blob);
-  if (m->type_id < 0 || m->type_id > 4) return SN_ERR_BADFORMAT;
-  int64_t cur = 4;
-  int32_t null_bytes = rd_i32(blob + cur); cur += 4;
-  if (null_bytes < 0 || (null_bytes & 7) || cur + null_bytes > len) return SN_ERR_BADFORMAT;
-  if (null_bytes) {
-    m->null_off = cur;
-    m->num_null_words = null_bytes >> 3;
-    cur += null_bytes;
-  }
-  if (m->type_id == SN_ENC_DICTIONARY || m->type_id == SN_ENC_BIG_DICTIONARY) {
-    if (cur + 4 > len) return SN_ERR_BADFORMAT;
-    int32_t n = rd_i32(blob + cur); cur += 4;
-    if (n < 0) return SN_ERR_BADFORMAT;
-    m->dict_n = n;
-    if (dtype == SN_TYPE_STRING) {
-      m->dict.reserve(n);
-      for (int32_t i = 0; i < n; i++) {
-        if (cur + 4 > len) return SN_ERR_BADFORMAT;
-        int32_t sz = rd_i32(blob + cur); cur += 4;
-        if (sz < 0 || cur + sz > len) return SN_ERR_BADFORMAT;
-        m->dict.emplace_back((const char *)blob + cur, (size_t)sz);
-        cur += sz;
-      }
-    } else if (dtype == SN_TYPE_INT32) {
-      for (int32_t i = 0; i < n; i++) { m->dict_i.push_back(rd_i32(blob + cur)); cur += 4; }
-    } else if (dtype == SN_TYPE_INT64) {
-      for (int32_t i = 0; i < n; i++) { m->dict_i.push_back(rd_i64(blob + cur)); cur += 8; }
-    } else return SN_ERR_UNSUPPORTED;
-    if (cur > len) return SN_ERR_BADFORMAT;
-  }
-  m->body_off = cur;
-  return SN_OK;
-}
-
-/* decode one delta blob into (pos, value, isnull) triples.
- * Restates ColumnDeltaDecoder.scala:31-120 on the host (deltas are bounded
- * by ColumnMaxDeltaRows, so this is O(10^4) host work per column). */
-static int decode_delta(const uint8_t *blob, int64_t len, sn_type_t dtype,
-                        Table *tab, int col,
-                        std::vector<int32_t> *pos, std::vector<double> *val,
-                        std::vector<uint8_t> *isnull) {
-  ColMeta m;
-  /* header first: typeId + nulls (over delta ENTRIES) */
-  if (!blob || len < 16) return SN_ERR_BADFORMAT;
-  int type_id = rd_i32(blob);
-  int64_t cur = 4;
-  int32_t null_bytes = rd_i32(blob + cur); cur += 4;
-  if (null_bytes < 0 || (null_bytes & 7)) return SN_ERR_BADFORMAT;
-  const uint8_t *nullw = null_bytes ? blob + cur : nullptr;
-  cur += null_bytes;
-  /* positions section (ColumnDeltaDecoder.initialize :45-58) */
-  int32_t npos = rd_i32(blob + cur + 4);
-  if (npos < 0) return SN_ERR_BADFORMAT;
-  const uint8_t *posp = blob + cur + 8;
-  cur = cur + 8 + (int64_t)npos * 4;
-  cur = (cur + 7) & ~7ll;
-  if (cur > len) return SN_ERR_BADFORMAT;
-  /* body (encoding-specific) */
-  m.type_id = type_id;
-  int32_t dict_n = 0;
-  std::vector<std::string> dict;
-  std::vector<int64_t> dict_i;
-  if (type_id == SN_ENC_DICTIONARY || type_id == SN_ENC_BIG_DICTIONARY) {
-    dict_n = rd_i32(blob + cur); cur += 4;
-    if (dtype == SN_TYPE_STRING) {
-      for (int32_t i = 0; i < dict_n; i++) {
-        int32_t sz = rd_i32(blob + cur); cur += 4;
-        dict.emplace_back((const char *)blob + cur, (size_t)sz); cur += sz;
-      }
-    } else {
-      int w = dtype == SN_TYPE_INT64 ? 8 : 4;
-      for (int32_t i = 0; i < dict_n; i++) {
-        dict_i.push_back(w == 8 ? rd_i64(blob + cur) : rd_i32(blob + cur)); cur += w;
-      }
-    }
-  } else if (type_id != SN_ENC_UNCOMPRESSED) {
-    return SN_ERR_UNSUPPORTED;  /* RLE deltas not produced by this build */
-  }
-  const uint8_t *body = blob + cur;
-  int nnp = 0;
-  int64_t var_cur = 0;
-  for (int32_t i = 0; i < npos; i++) {
-    int32_t p = rd_i32(posp + (int64_t)i * 4);
-    bool nul = nullw && ((rd_i64(nullw + ((i >> 6) << 3)) >> (i & 63)) & 1);
-    pos->push_back(p);
-    isnull->push_back(nul ? 1 : 0);
-    if (nul) { val->push_back(0.0); continue; }
-    double v = 0.0;
-    if (type_id == SN_ENC_UNCOMPRESSED) {
-      switch (dtype) {
-        case SN_TYPE_DOUBLE: v = rd_f64(body + (int64_t)nnp * 8); break;
-        case SN_TYPE_FLOAT:  v = rd_f32(body + (int64_t)nnp * 4); break;
-        case SN_TYPE_INT32:  v = (double)rd_i32(body + (int64_t)nnp * 4); break;
-        case SN_TYPE_INT64: {
-          /* carry RAW BITS (exact beyond 2^53, like the base-column path);
-           * every consumer of int64 patch values bitcasts back */
-          int64_t iv = rd_i64(body + (int64_t)nnp * 8);
-          memcpy(&v, &iv, 8);
-          break;
-        }
-        case SN_TYPE_INT16:  v = (double)rd_i16(body + (int64_t)nnp * 2); break;
-        case SN_TYPE_STRING: {
-          int32_t sz = rd_i32(body + var_cur);
-          std::string s((const char *)body + var_cur + 4, (size_t)sz);
-          var_cur += 4 + sz;
-          /* intern into the table-global dictionary */
-          auto &gi = tab->gdict_idx[col];
-          auto it = gi.find(s);
-          int32_t gid;
-          if (it == gi.end()) {
-            gid = (int32_t)tab->gdict[col].size();
-            tab->gdict[col].push_back(s);
-            gi.emplace(s, gid);
-            if ((int32_t)s.size() > tab->gdict_maxlen[col])
-              tab->gdict_maxlen[col] = (int32_t)s.size();
-          } else gid = it->second;
-          v = (double)gid;
-          break;
-        }
-        default: return SN_ERR_UNSUPPORTED;
-      }
-    } else { /* dictionary-encoded delta body */
-      int32_t idx = m.type_id == SN_ENC_DICTIONARY
-          ? (int32_t)(uint16_t)rd_i16(body + (int64_t)nnp * 2)
-          : rd_i32(body + (int64_t)nnp * 4);
-      if (dtype == SN_TYPE_STRING) {
-        if (idx >= dict_n) { isnull->back() = 1; val->push_back(0.0); nnp++; continue; }
-        auto &gi = tab->gdict_idx[col];
-        const std::string &s = dict[idx];
-        auto it = gi.find(s);
-        int32_t gid;
-        if (it == gi.end()) {
-          gid = (int32_t)tab->gdict[col].size();
-          tab->gdict[col].push_back(s);
-          gi.emplace(s, gid);
-          if ((int32_t)s.size() > tab->gdict_maxlen[col])
-            tab->gdict_maxlen[col] = (int32_t)s.size();
-        } else gid = it->second;
-        v = (double)gid;
-      } else if (dtype == SN_TYPE_INT64) {
-        int64_t iv = dict_i[idx];
-        memcpy(&v, &iv, 8);              /* raw bits, same as above */
-      } else {
-        v = (double)dict_i[idx];
-      }
-    }
-    val->push_back(v);
-    nnp++;
-  }
-  return SN_OK;
 }
 
 /* upload helper */
@@ -1185,436 +958,504 @@ static bool narrow_eligible(const Table *t, const Batch &b, int c) {
          b.cols[c].num_null_words == 0;
 }
 
+/* ---- one of each: batch sizing, bounds sizing, dictionary interning ---- */
+
+static void batch_init(Batch &b, int nc, int64_t uuid, int32_t bucket,
+                       int32_t rows) {
+  b.uuid = uuid;
+  b.bucket = bucket;
+  b.num_rows = rows;
+  b.cols.resize(nc);
+  b.col_dev.resize(nc);
+  b.nullpfx_dev.resize(nc, nullptr);
+  b.patch_dev.resize(nc);
+  b.patch_host.resize(nc);
+  b.had_patches.assign(nc, 0);
+  b.rle_ends_dev.resize(nc, nullptr);
+  b.rle_vals_dev.resize(nc, nullptr);
+  b.rle_n.resize(nc, 0);
+  b.dictmap_cache.resize(nc);
+  b.narrow.resize(nc);
+  b.is_raw.assign(nc, 0);
+}
+
+/* size the stats vectors with every column unbounded and null-free; whoever
+ * knows a column's bounds fills them in and clears bounds_null[c] */
+static void alloc_bounds(Batch &b, int nc) {
+  b.lo_d.resize(nc); b.hi_d.resize(nc);
+  b.lo_i.resize(nc); b.hi_i.resize(nc);
+  b.null_count.assign(nc, 0);
+  b.bounds_null.assign(nc, 1);
+}
+
+/* id of s in column c's table-global dictionary, appended when new; the
+ * caller holds t->mu */
+static int32_t intern(Table *t, int c, const std::string &s) {
+  auto it = t->gdict_idx[c].find(s);
+  if (it != t->gdict_idx[c].end()) return it->second;
+  const int32_t gid = (int32_t)t->gdict[c].size();
+  t->gdict[c].push_back(s);
+  t->gdict_idx[c].emplace(s, gid);
+  if ((int32_t)s.size() > t->gdict_maxlen[c])
+    t->gdict_maxlen[c] = (int32_t)s.size();
+  return gid;
+}
+
+static void intern_batch_dicts(Table *t, Batch &b) {
+  for (int c = 0; c < (int)t->schema.size(); c++) {
+    if (t->schema[c].dtype != SN_TYPE_STRING || b.cols[c].dict.empty())
+      continue;
+    auto &l2g = b.cols[c].local2global;
+    l2g.reserve(b.cols[c].dict.size());
+    for (auto &s : b.cols[c].dict) l2g.push_back(intern(t, c, s));
+  }
+}
+
 /* ---- batch mutation processing (shared by sn_batch_put and
  * sn_batch_mutate — the reference writes delete masks and delta blobs to
  * region entries of an EXISTING batch after UPDATE/DELETE statements;
  * the ColumnBatchIterator hands the current state per scan) ---- */
 
+/* delete mask -> bitmap (ColumnDeleteDecoder.scala:24-55 semantics); the mask
+ * is cumulative, so it REPLACES any previous one.  A mask that does not parse
+ * leaves the batch as it was. */
 static int32_t apply_delete_mask(sn_engine *e, Batch &b,
                                  const sn_buf *delete_mask) {
-  /* delete mask -> bitmap (ColumnDeleteDecoder.scala:24-55 semantics);
-   * the mask is cumulative, so it REPLACES any previous one */
-  b.has_deletes = false;
+  const uint8_t *pos = nullptr;
+  int32_t n = 0;
+  if (delete_mask && delete_mask->data &&
+      parse_delete_mask((const uint8_t *)delete_mask->data, delete_mask->len,
+                        &pos, &n) != SN_OK)
+    return fail(SN_ERR_BADFORMAT, delete_mask->len < 12
+                    ? "delete mask shorter than its header" : "bad delete mask");
+  b.has_deletes = n > 0;
   b.del_bm_dev = nullptr;
-  if (delete_mask && delete_mask->data && delete_mask->len < 12)
-    return fail(SN_ERR_BADFORMAT, "delete mask shorter than its header");
-  if (delete_mask && delete_mask->data && delete_mask->len >= 12) {
-    const uint8_t *dm = (const uint8_t *)delete_mask->data;
-    int32_t n = rd_i32(dm + 8);
-    if (n < 0 || 12 + (int64_t)n * 4 > delete_mask->len)
-      return fail(SN_ERR_BADFORMAT, "bad delete mask");
-    if (n > 0) {
-      b.has_deletes = true;
-      std::vector<uint64_t> bm(((size_t)b.num_rows + 63) / 64, 0);
-      for (int32_t i = 0; i < n; i++) {
-        int32_t p = rd_i32(dm + 12 + (int64_t)i * 4);
-        if (p >= 0 && p < b.num_rows) bm[p >> 6] |= 1ull << (p & 63);
-      }
-      b.del_bm_dev = (const uint64_t *)up(e, bm.data(), bm.size() * 8);
+  if (n > 0) {
+    std::vector<uint64_t> bm(((size_t)b.num_rows + 63) / 64, 0);
+    for (int32_t i = 0; i < n; i++) {
+      int32_t p = rd_i32(pos + (int64_t)i * 4);
+      if (p >= 0 && p < b.num_rows) bm[p >> 6] |= 1ull << (p & 63);
     }
+    b.del_bm_dev = (const uint64_t *)up(e, bm.data(), bm.size() * 8);
   }
-
   return SN_OK;
 }
 
-static int32_t apply_deltas(sn_engine *e, Table *t, Batch &b,
-                            const sn_buf *deltas) {
-  /* update deltas -> host-merged patches (delta1 overrides delta2,
-   * UpdatedColumnDecoder.scala:69-115).  Delta blobs are cumulative for
-   * their batch (the encoder merges upward), so the decoded set REPLACES
-   * any previous patch state; values already materialized into the body
-   * are simply rewritten with the same bytes. */
+/* per column: (delta1, delta2), empty where the caller passed none */
+typedef std::vector<std::pair<DeltaRows, DeltaRows>> ColDeltas;
+
+/* decode every delta blob before anything is applied: this touches neither
+ * the batch nor the table, so a corrupt blob changes nothing */
+static int32_t decode_deltas(const Table *t, const sn_buf *deltas,
+                             ColDeltas *out) {
   const int nc = (int)t->schema.size();
-  if (deltas) {
-    for (int c = 0; c < nc; c++) {
-      const sn_buf &d1 = deltas[c * 2], &d2 = deltas[c * 2 + 1];
-      if (!d1.data && !d2.data) continue;
-      /* deltas may arrive with a positive row count too (the reference
-       * signals them via the stats row's negative batchCount); either way
-       * the batch must never stats-skip — base bounds don't cover patches */
-      b.has_deltas = true;
-      b.patch_host[c] = Patch();          /* cumulative: replace prior state */
-      b.patch_dev[c] = Batch::PatchDev();
-      std::vector<int32_t> p1, p2;
-      std::vector<double> v1, v2;
-      std::vector<uint8_t> n1, n2;
-      if (d2.data) {
-        int rc = decode_delta((const uint8_t *)d2.data, d2.len, t->schema[c].dtype,
-                              t, c, &p2, &v2, &n2);
-        if (rc != SN_OK) return fail(rc, "delta2 decode col %d", c);
-      }
-      if (d1.data) {
-        int rc = decode_delta((const uint8_t *)d1.data, d1.len, t->schema[c].dtype,
-                              t, c, &p1, &v1, &n1);
-        if (rc != SN_OK) return fail(rc, "delta1 decode col %d", c);
-      }
-      /* merge: start from delta2, override with delta1 */
-      std::map<int32_t, std::pair<double, uint8_t>> merged;
-      for (size_t i = 0; i < p2.size(); i++) merged[p2[i]] = { v2[i], n2[i] };
-      for (size_t i = 0; i < p1.size(); i++) merged[p1[i]] = { v1[i], n1[i] };
-      Patch &P = b.patch_host[c];
-      for (auto &kv : merged) {
-        P.pos.push_back(kv.first);
-        P.val.push_back(kv.second.first);
-        P.isnull.push_back(kv.second.second);
-      }
-      if (P.pos.empty()) continue;
-      b.had_patches[c] = 1;
-      /* device structures */
-      std::vector<uint64_t> bm(((size_t)b.num_rows + 63) / 64, 0);
-      for (int32_t p : P.pos) if (p >= 0 && p < b.num_rows) bm[p >> 6] |= 1ull << (p & 63);
-      std::vector<uint64_t> nbm((P.pos.size() + 63) / 64, 0);
-      bool any_null = false;
-      for (size_t i = 0; i < P.isnull.size(); i++)
-        if (P.isnull[i]) { nbm[i >> 6] |= 1ull << (i & 63); any_null = true; }
-      auto &pd = b.patch_dev[c];
-      pd.n = (int32_t)P.pos.size();
-      pd.bm = (const uint64_t *)up(e, bm.data(), bm.size() * 8);
-      pd.pos = (const int32_t *)up(e, P.pos.data(), P.pos.size() * 4);
-      pd.val = (const double *)up(e, P.val.data(), P.val.size() * 8);
-      pd.nullbm = any_null ? (const uint64_t *)up(e, nbm.data(), nbm.size() * 8) : nullptr;
-
-      /* materialize value-only patches straight into the device body when
-       * the base column is null-free fixed-width: the batch then scans
-       * clean (query-compiled kernels apply).  Scan results are identical
-       * by construction — read_general would hand back exactly these
-       * values; the host blob (sn_table_get_blob) keeps the base bytes. */
-      if (e->has_gpu && !any_null && b.cols[c].num_null_words == 0 &&
-          b.cols[c].type_id == SN_ENC_UNCOMPRESSED) {
-        int k = -1;
-        switch (t->schema[c].dtype) {
-          case SN_TYPE_DOUBLE: k = SN_K_F64; break;
-          case SN_TYPE_FLOAT:  k = SN_K_F32; break;
-          case SN_TYPE_INT32:  k = SN_K_I32; break;
-          case SN_TYPE_INT64:  k = SN_K_I64; break;
-          case SN_TYPE_INT16:  k = SN_K_I16; break;
-          default: break;
-        }
-        if (k >= 0) {
-          void *body = (uint8_t *)(uintptr_t)b.col_dev[c] + b.cols[c].body_off;
-          if (sn_launch_patch_apply(body, pd.pos, pd.val, pd.n, k,
-                                    e->stream) == 0) {
-            pd = Batch::PatchDev();
-            P = Patch();
-            /* the body changed under the sidecar: rebuild it behind the
-             * patch kernel (an overflow drops it at the next query) */
-            if (k == SN_K_F64 && b.narrow[c].block) narrow_launch(e, t, b, c);
-          }
-        }
-      }
+  out->resize(deltas ? nc : 0);
+  for (int c = 0; c < (int)out->size(); c++) {
+    for (int j = 1; j >= 0; j--) {
+      const sn_buf &d = deltas[c * 2 + j];
+      if (!d.data) continue;
+      int rc = decode_delta((const uint8_t *)d.data, d.len, t->schema[c].dtype,
+                            j ? &(*out)[c].second : &(*out)[c].first);
+      if (rc != SN_OK) return fail(rc, "delta%d decode col %d", j + 1, c);
     }
   }
-
   return SN_OK;
 }
 
+/* delta2 then delta1 (delta1 overrides, UpdatedColumnDecoder.scala:69-115)
+ * into one patch sorted by row; string values are interned here and travel
+ * as table-global ids.  The caller holds t->mu. */
+static void merge_patch(Table *t, int c, const DeltaRows &d1,
+                        const DeltaRows &d2, Patch *P) {
+  std::map<int32_t, std::pair<double, uint8_t>> merged;
+  for (const DeltaRows *d : { &d2, &d1 })
+    for (size_t i = 0; i < d->pos.size(); i++) {
+      double v = d->val[i];
+      if (d->sidx[i] >= 0) v = (double)intern(t, c, d->strs[d->sidx[i]]);
+      merged[d->pos[i]] = { v, d->isnull[i] };
+    }
+  for (auto &kv : merged) {
+    P->pos.push_back(kv.first);
+    P->val.push_back(kv.second.first);
+    P->isnull.push_back(kv.second.second);
+  }
+}
+
+/* device form of a patch: row bitmap, positions, values, null bitmap over
+ * patch entries (absent when no entry writes NULL) */
+static Batch::PatchDev upload_patch(sn_engine *e, const Batch &b,
+                                    const Patch &P) {
+  std::vector<uint64_t> bm(((size_t)b.num_rows + 63) / 64, 0);
+  for (int32_t p : P.pos)
+    if (p >= 0 && p < b.num_rows) bm[p >> 6] |= 1ull << (p & 63);
+  std::vector<uint64_t> nbm((P.pos.size() + 63) / 64, 0);
+  bool any_null = false;
+  for (size_t i = 0; i < P.isnull.size(); i++)
+    if (P.isnull[i]) { nbm[i >> 6] |= 1ull << (i & 63); any_null = true; }
+  Batch::PatchDev pd;
+  pd.n = (int32_t)P.pos.size();
+  pd.bm = (const uint64_t *)up(e, bm.data(), bm.size() * 8);
+  pd.pos = (const int32_t *)up(e, P.pos.data(), P.pos.size() * 4);
+  pd.val = (const double *)up(e, P.val.data(), P.val.size() * 8);
+  pd.nullbm = any_null ? (const uint64_t *)up(e, nbm.data(), nbm.size() * 8)
+                       : nullptr;
+  return pd;
+}
+
+/* write value-only patches straight into the device body when the base
+ * column is null-free fixed-width: the batch then scans clean (query-compiled
+ * kernels apply).  Scan results are identical by construction — read_general
+ * would hand back exactly these values; the host blob (sn_table_get_blob)
+ * keeps the base bytes. */
+static void materialize_patch(sn_engine *e, const Table *t, Batch &b, int c) {
+  Batch::PatchDev &pd = b.patch_dev[c];
+  const std::vector<uint8_t> &isnull = b.patch_host[c].isnull;
+  const bool any_null = std::find(isnull.begin(), isnull.end(), 1) != isnull.end();
+  int k, width;
+  if (!e->has_gpu || any_null || b.cols[c].num_null_words != 0 ||
+      b.cols[c].type_id != SN_ENC_UNCOMPRESSED ||
+      !fixed_type(t->schema[c].dtype, &k, &width) || width < 2)
+    return;
+  void *body = (uint8_t *)(uintptr_t)b.col_dev[c] + b.cols[c].body_off;
+  if (sn_launch_patch_apply(body, pd.pos, pd.val, pd.n, k, e->stream) != 0)
+    return;
+  pd = Batch::PatchDev();
+  b.patch_host[c] = Patch();
+  /* the body changed under the sidecar: rebuild it behind the patch kernel
+   * (an overflow drops it at the next query) */
+  if (k == SN_K_F64 && b.narrow[c].block) narrow_launch(e, t, b, c);
+}
+
+/* decoded update deltas -> host-merged patches.  Delta blobs are cumulative
+ * for their batch (the encoder merges upward), so the decoded set REPLACES
+ * any previous patch state; values already materialized into the body are
+ * simply rewritten with the same bytes.  The caller holds t->mu. */
+static void apply_deltas(sn_engine *e, Table *t, Batch &b, const sn_buf *deltas,
+                         const ColDeltas &dec) {
+  for (int c = 0; c < (int)dec.size(); c++) {
+    if (!deltas[c * 2].data && !deltas[c * 2 + 1].data) continue;
+    /* deltas may arrive with a positive row count too (the reference
+     * signals them via the stats row's negative batchCount); either way
+     * the batch must never stats-skip — base bounds don't cover patches */
+    b.has_deltas = true;
+    Patch &P = b.patch_host[c];
+    P = Patch();                          /* cumulative: replace prior state */
+    b.patch_dev[c] = Batch::PatchDev();
+    merge_patch(t, c, dec[c].first, dec[c].second, &P);
+    if (P.pos.empty()) continue;
+    b.had_patches[c] = 1;
+    b.patch_dev[c] = upload_patch(e, b, P);
+    materialize_patch(e, t, b, c);
+  }
+}
+
+/* stats row parse (UnsafeRow: [null words][3*ncols+1 x 8B slots],
+ * ColumnStatsSchema, ColumnEncoding.scala:1015-1036); a row too short for
+ * the schema is ignored */
 static void apply_stats(Table *t, Batch &b, const sn_buf *stats) {
-  /* stats row parse (UnsafeRow: [null words][3*ncols+1 x 8B slots],
-   * ColumnStatsSchema, ColumnEncoding.scala:1015-1036) */
+  if (!stats || !stats->data) return;
   const int nc = (int)t->schema.size();
-  if (stats && stats->data) {
-    const uint8_t *sp = (const uint8_t *)stats->data;
-    int32_t num_fields = nc * 3 + 1;
-    int32_t nwords = (num_fields + 63) >> 6;
-    if (stats->len >= (int64_t)nwords * 8 + (int64_t)num_fields * 8) {
-      const uint8_t *bits = sp;
-      const uint8_t *slots = sp + (int64_t)nwords * 8;
-      auto bit = [&](int f) {
-        return (rd_i64(bits + ((f >> 6) << 3)) >> (f & 63)) & 1;
-      };
-      b.lo_d.resize(nc); b.hi_d.resize(nc);
-      b.lo_i.resize(nc); b.hi_i.resize(nc);
-      b.null_count.resize(nc); b.bounds_null.resize(nc);
-      for (int c = 0; c < nc; c++) {
-        int f_lo = 1 + c * 3, f_hi = 2 + c * 3, f_nc = 3 + c * 3;
-        b.bounds_null[c] = bit(f_lo) || bit(f_hi);
-        b.null_count[c] = bit(f_nc) ? 0 : rd_i32(slots + (int64_t)f_nc * 8);
-        if (b.bounds_null[c]) continue;
-        switch (t->schema[c].dtype) {
-          case SN_TYPE_DOUBLE:
-            b.lo_d[c] = rd_f64(slots + (int64_t)f_lo * 8);
-            b.hi_d[c] = rd_f64(slots + (int64_t)f_hi * 8); break;
-          case SN_TYPE_FLOAT:
-            b.lo_d[c] = rd_f32(slots + (int64_t)f_lo * 8);
-            b.hi_d[c] = rd_f32(slots + (int64_t)f_hi * 8); break;
-          case SN_TYPE_INT64:
-            b.lo_i[c] = rd_i64(slots + (int64_t)f_lo * 8);
-            b.hi_i[c] = rd_i64(slots + (int64_t)f_hi * 8); break;
-          case SN_TYPE_STRING:
-            b.bounds_null[c] = 1; break;
-          default:
-            b.lo_i[c] = rd_i32(slots + (int64_t)f_lo * 8);
-            b.hi_i[c] = rd_i32(slots + (int64_t)f_hi * 8);
-        }
-      }
-      b.stats_valid = true;
+  const int32_t num_fields = nc * 3 + 1;
+  BlobReader r((const uint8_t *)stats->data, stats->len);
+  const uint8_t *bits = r.array((num_fields + 63) >> 6, 8);
+  const uint8_t *slots = r.array(num_fields, 8);
+  if (!r.ok) return;
+  auto bit = [&](int f) {
+    return (rd_i64(bits + ((f >> 6) << 3)) >> (f & 63)) & 1;
+  };
+  alloc_bounds(b, nc);
+  for (int c = 0; c < nc; c++) {
+    const uint8_t *lo = slots + (int64_t)(1 + c * 3) * 8, *hi = lo + 8;
+    const int f_lo = 1 + c * 3, f_hi = 2 + c * 3, f_nc = 3 + c * 3;
+    b.bounds_null[c] = bit(f_lo) || bit(f_hi);
+    b.null_count[c] = bit(f_nc) ? 0 : rd_i32(hi + 8);
+    if (b.bounds_null[c]) continue;
+    switch (t->schema[c].dtype) {
+      case SN_TYPE_DOUBLE: b.lo_d[c] = rd_f64(lo); b.hi_d[c] = rd_f64(hi); break;
+      case SN_TYPE_FLOAT:  b.lo_d[c] = rd_f32(lo); b.hi_d[c] = rd_f32(hi); break;
+      case SN_TYPE_INT64:  b.lo_i[c] = rd_i64(lo); b.hi_i[c] = rd_i64(hi); break;
+      case SN_TYPE_STRING: b.bounds_null[c] = 1; break;
+      default:             b.lo_i[c] = rd_i32(lo); b.hi_i[c] = rd_i32(hi);
     }
   }
-
+  b.stats_valid = true;
 }
 
-/* one encoded column blob -> device-resident state (decompress, parse,
- * transcode/materialize, validate, upload, aux) — batch-local, no table
+/* ---- the stages of one encoded column's put, in the order
+ * process_encoded_col runs them ---- */
+
+/* the bytes that get stored for a column: the caller's, their decompressed
+ * form, or a re-encoding synthesized here */
+struct ColBlob {
+  const uint8_t *blob = nullptr;
+  int64_t len = 0;
+  std::vector<uint8_t> decomp, synth;   /* own the bytes that are not the caller's */
+  bool lz4 = false;                     /* the caller's bytes are an LZ4 wrapper */
+};
+
+/* stage 1: strip the compression wrapper, if any */
+static int32_t unwrap_blob(const sn_buf &column, ColBlob *cb) {
+  cb->blob = (const uint8_t *)column.data;
+  cb->len = column.len;
+  int dec = maybe_decompress(cb->blob, cb->len, &cb->decomp);
+  if (dec < 0) return dec;
+  if (dec == 1) {
+    cb->lz4 = rd_i32(cb->blob) == -1;
+    cb->blob = cb->decomp.data();
+    cb->len = (int64_t)cb->decomp.size();
+  }
+  return SN_OK;
+}
+
+/* stage 3: what a kernel would index by row count must be there.  A corrupt
+ * dictionary index would walk the kernel off the end of the local->global
+ * map; a short fixed-width body would have it read a neighbouring block. */
+static int32_t check_col_body(const ColBlob &cb, const ColMeta &m,
+                              sn_type_t dtype, int32_t rows, int c) {
+  if (dtype == SN_TYPE_STRING && !m.dict.empty()) {
+    int64_t bad;
+    if (check_dict_indices(cb.blob, cb.len, m, rows, (int32_t)m.dict.size(),
+                           &bad) == SN_OK)
+      return SN_OK;
+    if (bad < 0)
+      return fail(SN_ERR_BADFORMAT, "dictionary index array truncated col %d", c);
+    return fail(SN_ERR_BADFORMAT,
+                "dictionary index %d out of range [0,%d] at row %lld col %d",
+                dict_index(cb.blob + m.body_off, dict_index_width(m.type_id), bad),
+                (int)m.dict.size(), (long long)bad, c);
+  }
+  const int width = sn_type_width(dtype);
+  if (m.type_id == SN_ENC_UNCOMPRESSED && width > 0 &&
+      check_fixed_body(cb.blob, cb.len, m, rows, width) != SN_OK)
+    return fail(SN_ERR_BADFORMAT,
+                "column %d body shorter than its %d non-null rows", c,
+                (int)(rows - count_nulls(cb.blob, m)));
+  return SN_OK;
+}
+
+/* stage 4: encodings no kernel reads are re-encoded at put, the same idea as
+ * decompress-on-put: var-width strings become BIG_DICTIONARY (global
+ * interning, premultiplied maps, pushdown equality and group keys then apply
+ * wholesale), int dictionaries become a plain body (the plain I32/I64 scan
+ * path, JIT-eligible).  The synthesized blob replaces cb's and is re-parsed. */
+static int32_t reencode_col(ColBlob *cb, ColMeta *m, sn_type_t dtype,
+                            int32_t rows, int c) {
+  const bool dict_enc = m->type_id == SN_ENC_DICTIONARY ||
+                        m->type_id == SN_ENC_BIG_DICTIONARY;
+  const char *what;
+  if (dtype == SN_TYPE_STRING && m->type_id == SN_ENC_UNCOMPRESSED) {
+    what = "transcoded string col %d";
+    if (transcode_strings(cb->blob, cb->len, *m, rows, &cb->synth) != SN_OK)
+      return fail(SN_ERR_BADFORMAT, "string body truncated col %d", c);
+  } else if (dict_enc && dtype != SN_TYPE_STRING) {
+    what = "materialized dict col %d";
+    int64_t bad;
+    if (materialize_int_dict(cb->blob, cb->len, *m, dtype, rows, &cb->synth,
+                             &bad) != SN_OK) {
+      if (bad < 0)
+        return fail(SN_ERR_BADFORMAT,
+                    "dictionary index array truncated col %d", c);
+      return fail(SN_ERR_BADFORMAT,
+                  "dictionary index %d out of range [0,%d] col %d",
+                  dict_index(cb->blob + m->body_off,
+                             dict_index_width(m->type_id), bad), m->dict_n, c);
+    }
+  } else {
+    return SN_OK;
+  }
+  cb->blob = cb->synth.data();
+  cb->len = (int64_t)cb->synth.size();
+  *m = ColMeta();
+  int rc = parse_blob(cb->blob, cb->len, dtype, m);
+  return rc == SN_OK ? SN_OK : fail(rc, what, c);
+}
+
+/* f1 compressed-upload: an LZ4-wrapped blob ships its COMPRESSED bytes over
+ * PCIe (the host's decompressed copy served only parse and validation) and
+ * decodes wave-cooperatively on device into dst[0, len) — byte-identical
+ * output, ~2-4x less bus traffic per blob.  1 = decoded, 0 = not done (the
+ * caller copies the host bytes instead), negative = the device found the
+ * stream malformed. */
+static int32_t lz4_decode_on_device(sn_engine *e, const sn_buf &column,
+                                    char *dst, int64_t len, int c) {
+  const int64_t clen = column.len - 8;
+  /* the engine stream + error word are shared: one decode at a time
+   * (concurrent puts overlap their host work; device decodes queue) */
+  std::lock_guard<std::mutex> glz(e->lz4_mu);
+  void *cdev = e->arena.alloc((size_t)clen);
+  if (!e->lz4_err_dev) e->lz4_err_dev = (int32_t *)e->arena.alloc(64);
+  int32_t done = 0;
+  if (cdev && e->lz4_err_dev &&
+      hipMemcpy(cdev, (const uint8_t *)column.data + 8, (size_t)clen,
+                hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemsetAsync(e->lz4_err_dev, 0, 4, e->stream) == hipSuccess &&
+      sn_launch_lz4_decompress(cdev, clen, dst, len, e->lz4_err_dev,
+                               e->stream) == 0 &&
+      hipStreamSynchronize(e->stream) == hipSuccess) {
+    int32_t derr = -1;
+    (void)hipMemcpy(&derr, e->lz4_err_dev, 4, hipMemcpyDeviceToHost);
+    if (derr != 0)
+      return fail(SN_ERR_BADFORMAT, "device LZ4 decode failed (%d) col %d",
+                  derr, c);
+    done = 1;
+  }
+  if (cdev) e->arena.release(cdev, (size_t)clen);
+  return done;
+}
+
+/* stage 5: the blob into the arena, placed so the BODY is 16-byte aligned
+ * (the scan kernel issues 16 B/lane vector loads on the body; the 8-byte
+ * blob header would otherwise leave it 8-aligned).  Host-only engines keep
+ * the bytes for sn_table_get_blob: one host_blobs entry per column, in
+ * column order. */
+static int32_t upload_blob(sn_engine *e, Batch &b, int c, const ColBlob &cb,
+                           const sn_buf &column) {
+  const int64_t pad = (16 - (b.cols[c].body_off & 15)) & 15;
+  char *base = (char *)e->arena.alloc((size_t)cb.len + 16);
+  if (!base) return fail(SN_ERR_NOMEM, "HBM upload failed");
+  char *dst = base + pad;
+  if (e->arena.device < 0) {
+    memcpy(dst, cb.blob, (size_t)cb.len);
+    b.host_blobs.emplace_back(cb.blob, cb.blob + cb.len);
+  } else {
+    int32_t dev = cb.lz4 ? lz4_decode_on_device(e, column, dst, cb.len, c) : 0;
+    if (dev < 0) return dev;
+    if (dev == 0 && h2d_copy(e, dst, cb.blob, (size_t)cb.len) != hipSuccess)
+      return fail(SN_ERR_NOMEM, "HBM upload failed");
+  }
+  b.col_dev[c] = dst;
+  return SN_OK;
+}
+
+/* stage 6: RLE aux — (cumulative end, value-as-f64) per run, extracted on
+ * host (the decoder accumulates run lengths sequentially, which has no
+ * data-parallel analogue) */
+static int32_t build_rle_aux(sn_engine *e, const Table *t, Batch &b, int c,
+                             const ColBlob &cb) {
+  if (b.cols[c].type_id != SN_ENC_RUNLENGTH) return SN_OK;
+  const sn_type_t dt = t->schema[c].dtype;
+  int kind, w;
+  if (!fixed_type(dt, &kind, &w) ||
+      (kind != SN_K_I16 && kind != SN_K_I32 && kind != SN_K_I64))
+    return fail(SN_ERR_UNSUPPORTED, "RLE col %d dtype %d on GPU path", c, dt);
+  std::vector<int32_t> ends;
+  std::vector<double> vals;
+  extract_rle_runs(cb.blob, cb.len, b.cols[c], w, kind == SN_K_I64, &ends, &vals);
+  if (!ends.empty()) {
+    b.rle_ends_dev[c] = (const int32_t *)up(e, ends.data(), ends.size() * 4);
+    b.rle_vals_dev[c] = (const double *)up(e, vals.data(), vals.size() * 8);
+    b.rle_n[c] = (int32_t)ends.size();
+  }
+  return SN_OK;
+}
+
+/* stage 7: nulls in words [0, w) for each null word w */
+static void build_null_prefix(sn_engine *e, Batch &b, int c, const ColBlob &cb) {
+  const ColMeta &m = b.cols[c];
+  if (!m.num_null_words) return;
+  std::vector<uint32_t> pfx((size_t)m.num_null_words);
+  uint32_t acc = 0;
+  for (int w = 0; w < m.num_null_words; w++) {
+    pfx[w] = acc;
+    acc += (uint32_t)__builtin_popcountll(
+        (unsigned long long)rd_i64(cb.blob + m.null_off + (int64_t)w * 8));
+  }
+  b.nullpfx_dev[c] = (const uint32_t *)up(e, pfx.data(), pfx.size() * 4);
+}
+
+/* one encoded column blob -> device-resident state — batch-local, no table
  * lock; shared by sn_batch_put and sn_batch_put_raw */
 static int32_t process_encoded_col(sn_engine *e, Table *t, Batch &b, int c,
                                    const sn_buf &column) {
-  std::vector<uint8_t> decomp;
-    const uint8_t *blob = (const uint8_t *)column.data;
-    int64_t len = column.len;
-    int dec = maybe_decompress(blob, len, &decomp);
-    if (dec < 0) return dec;
-    if (dec == 1) { blob = decomp.data(); len = (int64_t)decomp.size(); }
-    int rc = parse_blob(blob, len, t->schema[c].dtype, &b.cols[c]);
-    if (rc != SN_OK) return fail(rc, "column %d blob parse failed", c);
-    if (t->schema[c].dtype == SN_TYPE_STRING && !b.cols[c].dict.empty()) {
-      /* validate the index array: a corrupt index would walk the kernel
-       * off the end of the local->global map (index == dict size is the
-       * NULL sentinel, DictionaryEncoding.scala:90) */
-      const ColMeta &dm = b.cols[c];
-      const int32_t dn = (int32_t)dm.dict.size();
-      const uint8_t *bodyp = blob + dm.body_off;
-      int w = dm.type_id == SN_ENC_DICTIONARY ? 2 : 4;
-      /* exactly one index per NON-NULL row; padding beyond is not data */
-      int64_t nnull = 0;
-      for (int32_t wi = 0; wi < dm.num_null_words; wi++)
-        nnull += __builtin_popcountll(
-            (unsigned long long)rd_i64(blob + dm.null_off + (int64_t)wi * 8));
-      int64_t nidx = (int64_t)b.num_rows - nnull;
-      if (nidx * w > len - dm.body_off)
-        return fail(SN_ERR_BADFORMAT, "dictionary index array truncated col %d", c);
-      for (int64_t i = 0; i < nidx; i++) {
-        int32_t ix = w == 2 ? (int32_t)(uint16_t)rd_i16(bodyp + i * 2)
-                            : rd_i32(bodyp + i * 4);
-        if (ix < 0 || ix > dn)
-          return fail(SN_ERR_BADFORMAT,
-                      "dictionary index %d out of range [0,%d] at row %lld col %d",
-                      ix, dn, (long long)i, c);
-      }
-    }
-    /* Var-width (non-dictionary) STRING bodies (Uncompressed.scala:117-160:
-     * [int32 size][bytes] sequential per non-null row) have no random-access
-     * layout a data-parallel kernel can consume; transcode them to
-     * Dictionary encoding at put (the same re-encode-on-put idea as the
-     * LZ4 wrapper and int-dict materialization below) so the existing
-     * dictionary machinery — global interning, premultiplied maps, pushdown
-     * equality, group keys — applies wholesale. */
-    std::vector<uint8_t> synth;
-    if (t->schema[c].dtype == SN_TYPE_STRING &&
-        b.cols[c].type_id == SN_ENC_UNCOMPRESSED) {
-      const ColMeta dm = b.cols[c];
-      const int32_t rows = b.num_rows;
-      const int32_t nwords = dm.num_null_words;
-      std::map<std::string, int32_t> didx;
-      std::vector<std::string> dict;
-      std::vector<int32_t> idx;
-      idx.reserve(rows);
-      int64_t cur = dm.body_off;
-      int64_t nnull = 0;
-      for (int32_t wi = 0; wi < nwords; wi++)
-        nnull += __builtin_popcountll(
-            (unsigned long long)rd_i64(blob + dm.null_off + (int64_t)wi * 8));
-      const int64_t nn_rows = rows - nnull;
-      int64_t dict_bytes = 0;
-      for (int64_t i = 0; i < nn_rows; i++) {
-        if (cur + 4 > len)
-          return fail(SN_ERR_BADFORMAT, "string body truncated col %d", c);
-        int32_t sz = rd_i32(blob + cur);
-        cur += 4;
-        if (sz < 0 || cur + sz > len)
-          return fail(SN_ERR_BADFORMAT, "string body truncated col %d", c);
-        std::string s((const char *)blob + cur, (size_t)sz);
-        cur += sz;
-        auto it = didx.find(s);
-        int32_t di;
-        if (it == didx.end()) {
-          di = (int32_t)dict.size();
-          dict_bytes += 4 + sz;
-          didx.emplace(std::move(s), di);
-          dict.push_back(std::string((const char *)blob + cur - sz, (size_t)sz));
-        } else di = it->second;
-        idx.push_back(di);
-      }
-      const int64_t nb = (int64_t)nwords * 8;
-      synth.resize(8 + nb + 4 + dict_bytes + (int64_t)idx.size() * 4);
-      int32_t tid3 = SN_ENC_BIG_DICTIONARY, nb32 = (int32_t)nb;
-      memcpy(synth.data(), &tid3, 4);
-      memcpy(synth.data() + 4, &nb32, 4);
-      if (nb) memcpy(synth.data() + 8, blob + dm.null_off, (size_t)nb);
-      uint8_t *w = synth.data() + 8 + nb;
-      int32_t dn = (int32_t)dict.size();
-      memcpy(w, &dn, 4); w += 4;
-      for (auto &s : dict) {
-        int32_t sz = (int32_t)s.size();
-        memcpy(w, &sz, 4); w += 4;
-        memcpy(w, s.data(), s.size()); w += s.size();
-      }
-      memcpy(w, idx.data(), idx.size() * 4);
-      blob = synth.data();
-      len = (int64_t)synth.size();
-      b.cols[c] = ColMeta();
-      int rc2 = parse_blob(blob, len, SN_TYPE_STRING, &b.cols[c]);
-      if (rc2 != SN_OK) return fail(rc2, "transcoded string col %d", c);
-    }
+  const sn_type_t dt = t->schema[c].dtype;
+  ColMeta &m = b.cols[c];
+  ColBlob cb;
+  int32_t rc = unwrap_blob(column, &cb);
+  if (rc != SN_OK) return rc;
+  rc = parse_blob(cb.blob, cb.len, dt, &m);
+  if (rc != SN_OK) return fail(rc, "column %d blob parse failed", c);
+  if ((rc = check_col_body(cb, m, dt, b.num_rows, c)) != SN_OK) return rc;
+  if ((rc = reencode_col(&cb, &m, dt, b.num_rows, c)) != SN_OK) return rc;
+  if ((rc = upload_blob(e, b, c, cb, column)) != SN_OK) return rc;
+  if ((rc = build_rle_aux(e, t, b, c, cb)) != SN_OK) return rc;
+  build_null_prefix(e, b, c, cb);
+  /* stage 8: low-cardinality doubles get a code sidecar from the uploaded
+   * (or device-decoded) body, behind whatever wrote it on the stream */
+  if (narrow_eligible(t, b, c) &&
+      narrow_prefix_fits(cb.blob + m.body_off, b.num_rows))
+    narrow_launch(e, t, b, c);
+  return SN_OK;
+}
 
-    /* int-typed dictionary columns (DictionaryEncoding over int32/int64,
-     * DictionaryEncoding.scala:85-137): materialize the values into a plain
-     * fixed-width body at put — decompress-on-put, like the LZ4 wrapper —
-     * so the scan runs the plain I32/I64 path (JIT-eligible).  Index ==
-     * numElements is the null sentinel (DictionaryEncoding.scala:90): such
-     * rows are folded into the synthesized null bitset. */
-    if ((b.cols[c].type_id == SN_ENC_DICTIONARY ||
-         b.cols[c].type_id == SN_ENC_BIG_DICTIONARY) &&
-        t->schema[c].dtype != SN_TYPE_STRING) {
-      const ColMeta dm = b.cols[c];
-      const sn_type_t dt = t->schema[c].dtype;
-      const int w = dm.type_id == SN_ENC_DICTIONARY ? 2 : 4;
-      const int vw = dt == SN_TYPE_INT64 ? 8 : 4;
-      const int32_t dn = dm.dict_n;
-      const int32_t rows = b.num_rows;
-      const int32_t nwords = (rows + 63) >> 6;
-      std::vector<uint64_t> nullw(nwords, 0);
-      if (dm.num_null_words) {
-        for (int32_t wi = 0; wi < dm.num_null_words && wi < nwords; wi++)
-          nullw[wi] = (uint64_t)rd_i64(blob + dm.null_off + (int64_t)wi * 8);
-      }
-      std::vector<int64_t> vals;
-      vals.reserve(rows);
-      const uint8_t *bodyp = blob + dm.body_off;
-      int64_t ii = 0;                     /* index cursor (one per non-null row) */
-      const int64_t navail = (len - dm.body_off) / w;
-      for (int32_t r = 0; r < rows; r++) {
-        if ((nullw[r >> 6] >> (r & 63)) & 1) continue;
-        if (ii >= navail)
-          return fail(SN_ERR_BADFORMAT, "dictionary index array truncated col %d", c);
-        int32_t ix = w == 2 ? (int32_t)(uint16_t)rd_i16(bodyp + ii * 2)
-                            : rd_i32(bodyp + ii * 4);
-        ii++;
-        if (ix < 0 || ix > dn)
-          return fail(SN_ERR_BADFORMAT,
-                      "dictionary index %d out of range [0,%d] col %d", ix, dn, c);
-        if (ix == dn) { nullw[r >> 6] |= 1ull << (r & 63); continue; }
-        vals.push_back(dm.dict_i[ix]);
-      }
-      bool any_null = false;
-      for (uint64_t wv : nullw) any_null |= wv != 0;
-      const int64_t nb = any_null ? (int64_t)nwords * 8 : 0;
-      synth.resize(8 + nb + (int64_t)vals.size() * vw);
-      int32_t tid0 = SN_ENC_UNCOMPRESSED, nb32 = (int32_t)nb;
-      memcpy(synth.data(), &tid0, 4);
-      memcpy(synth.data() + 4, &nb32, 4);
-      if (nb) memcpy(synth.data() + 8, nullw.data(), (size_t)nb);
-      uint8_t *vb = synth.data() + 8 + nb;
-      for (size_t i = 0; i < vals.size(); i++) {
-        if (vw == 8) memcpy(vb + i * 8, &vals[i], 8);
-        else { int32_t v32 = (int32_t)vals[i]; memcpy(vb + i * 4, &v32, 4); }
-      }
-      blob = synth.data();
-      len = (int64_t)synth.size();
-      b.cols[c] = ColMeta();
-      int rc2 = parse_blob(blob, len, dt, &b.cols[c]);
-      if (rc2 != SN_OK) return fail(rc2, "materialized dict col %d", c);
+/* host-only engines: scalar bounds of one raw column, so stats-skip still
+ * works without the device min/max */
+static void host_bounds(Batch &b, int nc, int c, sn_type_t dt, int w,
+                        const uint8_t *vals) {
+  if (b.bounds_null.empty()) alloc_bounds(b, nc);
+  if (dt == SN_TYPE_DOUBLE || dt == SN_TYPE_FLOAT) {
+    double mn = 0, mx = 0;
+    for (int32_t i = 0; i < b.num_rows; i++) {
+      double v = w == 8 ? rd_f64(vals + (int64_t)i * 8)
+                        : rd_f32(vals + (int64_t)i * 4);
+      if (i == 0 || v < mn) mn = v;
+      if (i == 0 || v > mx) mx = v;
     }
+    b.lo_d[c] = mn; b.hi_d[c] = mx;
+  } else {
+    int64_t mn = 0, mx = 0;
+    for (int32_t i = 0; i < b.num_rows; i++) {
+      int64_t v = w == 8 ? rd_i64(vals + (int64_t)i * 8)
+                : w == 4 ? rd_i32(vals + (int64_t)i * 4)
+                         : rd_i16(vals + (int64_t)i * 2);
+      if (i == 0 || v < mn) mn = v;
+      if (i == 0 || v > mx) mx = v;
+    }
+    b.lo_i[c] = mn; b.hi_i[c] = mx;
+  }
+  b.bounds_null[c] = 0;
+  b.stats_valid = true;
+}
 
-    /* upload blob, placed so the BODY is 16-byte aligned (the scan kernel
-     * issues 16 B/lane vector loads on the body; the 8-byte blob header
-     * would otherwise leave it 8-aligned).
-     * f1 compressed-upload: LZ4-wrapped blobs ship their COMPRESSED bytes
-     * over PCIe (the host decompressed copy serves only parse/validation)
-     * and decode wave-cooperatively on device into the blob slot —
-     * byte-identical output, ~2-4x less bus traffic per blob. */
-    {
-      int64_t pad = (16 - (b.cols[c].body_off & 15)) & 15;
-      char *base = (char *)e->arena.alloc((size_t)len + 16);
-      if (!base) return fail(SN_ERR_NOMEM, "HBM upload failed");
-      char *dst = base + pad;
-      bool dev_decoded = false;
-      if (e->arena.device >= 0 && dec == 1 &&
-          rd_i32((const uint8_t *)column.data) == -1 /* LZ4 */) {
-        const int64_t clen = column.len - 8;
-        /* the engine stream + error word are shared: one decode at a time
-         * (concurrent puts overlap their host work; device decodes queue) */
-        std::lock_guard<std::mutex> glz(e->lz4_mu);
-        void *cdev = e->arena.alloc((size_t)clen);
-        if (!e->lz4_err_dev)
-          e->lz4_err_dev = (int32_t *)e->arena.alloc(64);
-        if (cdev && e->lz4_err_dev &&
-            hipMemcpy(cdev, (const uint8_t *)column.data + 8,
-                      (size_t)clen, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemsetAsync(e->lz4_err_dev, 0, 4, e->stream) == hipSuccess &&
-            sn_launch_lz4_decompress(cdev, clen, dst, len, e->lz4_err_dev,
-                                     e->stream) == 0 &&
-            hipStreamSynchronize(e->stream) == hipSuccess) {
-          int32_t derr = -1;
-          (void)hipMemcpy(&derr, e->lz4_err_dev, 4, hipMemcpyDeviceToHost);
-          if (derr != 0)
-            return fail(SN_ERR_BADFORMAT,
-                        "device LZ4 decode failed (%d) col %d", derr, c);
-          dev_decoded = true;
-        }
-        if (cdev) e->arena.release(cdev, (size_t)clen);
-      }
-      if (!dev_decoded) {
-        if (e->arena.device >= 0) {
-          if (h2d_copy(e, dst, blob, (size_t)len) != hipSuccess)
-            return fail(SN_ERR_NOMEM, "HBM upload failed");
-        } else {
-          memcpy(dst, blob, (size_t)len);
-        }
-      }
-      b.col_dev[c] = dst;
-    }
-    if (e->arena.device < 0) {
-      b.host_blobs.emplace_back(blob, blob + len);
-    }
-    /* RLE aux: extract (cumulative end, value-as-f64) per run on host
-     * (the blob stores [value][int32 run-length] entries; the decoder
-     * accumulates — RunLengthEncoding.scala:99-172) */
-    if (b.cols[c].type_id == SN_ENC_RUNLENGTH) {
-      sn_type_t dt = t->schema[c].dtype;
-      int w = dt == SN_TYPE_INT16 ? 2 : dt == SN_TYPE_INT32 ? 4 :
-              dt == SN_TYPE_INT64 ? 8 : 0;
-      if (w == 0)
-        return fail(SN_ERR_UNSUPPORTED, "RLE col %d dtype %d on GPU path", c, dt);
-      std::vector<int32_t> ends;
-      std::vector<double> vals;
-      int64_t cur = b.cols[c].body_off;
-      int32_t acc = 0;
-      while (cur + w + 4 <= len) {
-        int64_t v = w == 2 ? rd_i16(blob + cur) : w == 4 ? rd_i32(blob + cur)
-                                                         : rd_i64(blob + cur);
-        acc += rd_i32(blob + cur + w);
-        ends.push_back(acc);
-        if (dt == SN_TYPE_INT64) {
-          double d; memcpy(&d, &v, 8); vals.push_back(d);  /* raw bits */
-        } else vals.push_back((double)v);
-        cur += w + 4;
-      }
-      if (!ends.empty()) {
-        b.rle_ends_dev[c] = (const int32_t *)up(e, ends.data(), ends.size() * 4);
-        b.rle_vals_dev[c] = (const double *)up(e, vals.data(), vals.size() * 8);
-        b.rle_n[c] = (int32_t)ends.size();
-      }
-    }
-
-    /* null prefix aux */
-    if (b.cols[c].num_null_words) {
-      const uint8_t *nw = blob + b.cols[c].null_off;
-      int W = b.cols[c].num_null_words;
-      std::vector<uint32_t> pfx((size_t)W);
-      uint32_t acc = 0;
-      for (int w = 0; w < W; w++) {
-        pfx[w] = acc;
-        acc += (uint32_t)__builtin_popcountll((unsigned long long)rd_i64(nw + (int64_t)w * 8));
-      }
-      b.nullpfx_dev[c] = (const uint32_t *)up(e, pfx.data(), pfx.size() * 4);
-    }
-    /* low-cardinality doubles: code sidecar from the uploaded (or
-     * device-decoded) body */
-    if (narrow_eligible(t, b, c) &&
-        b.cols[c].body_off + (int64_t)b.num_rows * 8 <= len &&
-        narrow_prefix_fits(blob + b.cols[c].body_off, b.num_rows))
-      narrow_launch(e, t, b, c);
+/* one raw (non-null, fixed-width) value array -> device blob
+ * [typeId=0][nullBytes=0][body]: header at base+8 (8-aligned), body at
+ * base+16 (16-aligned — arena blocks are 256-aligned); blob pointer =
+ * base+8, body_off = 8.  On device the bounds come from an async min/max into
+ * sd (the caller zeroed it on the same stream); host-only from host_bounds. */
+static int32_t put_raw_col(sn_engine *e, Table *t, Batch &b, int c,
+                           const sn_buf &raw, unsigned long long *sd) {
+  const int nc = (int)t->schema.size();
+  const sn_type_t dt = t->schema[c].dtype;
+  int kind, w;
+  if (!fixed_type(dt, &kind, &w) || w < 2)
+    return fail(SN_ERR_UNSUPPORTED, "raw column %d dtype %d", c, (int)dt);
+  if (raw.len != (int64_t)b.num_rows * w)
+    return fail(SN_ERR_BADARG, "raw column %d length", c);
+  char *base = (char *)e->arena.alloc((size_t)raw.len + 16);
+  if (!base) return fail(SN_ERR_NOMEM, "HBM upload failed");
+  char *body = base + 16;
+  const int32_t hdr[2] = { SN_ENC_UNCOMPRESSED, 0 };
+  b.cols[c].type_id = SN_ENC_UNCOMPRESSED;
+  b.cols[c].body_off = 8;
+  b.col_dev[c] = base + 8;
+  if (e->arena.device < 0) {
+    memcpy(base + 8, hdr, 8);
+    memcpy(body, raw.data, (size_t)raw.len);
+    b.host_blobs.emplace_back((const uint8_t *)base + 8,
+                              (const uint8_t *)body + raw.len);
+    host_bounds(b, nc, c, dt, w, (const uint8_t *)raw.data);
     return SN_OK;
+  }
+  if (hipMemcpy(base + 8, hdr, 8, hipMemcpyHostToDevice) != hipSuccess ||
+      h2d_copy(e, body, raw.data, (size_t)raw.len) != hipSuccess)
+    return fail(SN_ERR_NOMEM, "HBM upload failed");
+  if (sn_launch_col_minmax(body, b.num_rows, kind, sd + c, sd + nc + c,
+                           e->stream) != 0)
+    return fail(SN_ERR_GENERIC, "stats kernel");
+  b.is_raw[c] = 1;
+  if (dt == SN_TYPE_DOUBLE &&
+      narrow_prefix_fits((const uint8_t *)raw.data, b.num_rows))
+    narrow_launch(e, t, b, c);
+  return SN_OK;
 }
 
 /* f2 fast ingest: fixed-width NON-NULL columns arrive as RAW value arrays
@@ -1636,22 +1477,9 @@ extern "C" int32_t sn_batch_put_raw(sn_engine *e, int32_t table,
     return SN_OK;
   const int nc = (int)t->schema.size();
   Batch b;
-  b.uuid = uuid;
-  b.bucket = bucket_id;
-  b.num_rows = num_rows;
-  b.cols.resize(nc);
-  b.col_dev.resize(nc);
-  b.nullpfx_dev.resize(nc, nullptr);
-  b.patch_dev.resize(nc);
-  b.patch_host.resize(nc);
-  b.had_patches.assign(nc, 0);
-  b.rle_ends_dev.resize(nc, nullptr);
-  b.rle_vals_dev.resize(nc, nullptr);
-  b.rle_n.resize(nc, 0);
-  b.dictmap_cache.resize(nc);
-  b.narrow.resize(nc);
-  b.is_raw.assign(nc, 0);
+  batch_init(b, nc, uuid, bucket_id, num_rows);
 
+  /* both memsets go on the stream before any column's min/max launch */
   unsigned long long *sd = nullptr;
   if (e->has_gpu) {
     sd = (unsigned long long *)e->arena.alloc((size_t)nc * 16);
@@ -1662,85 +1490,12 @@ extern "C" int32_t sn_batch_put_raw(sn_engine *e, int32_t table,
   }
   bool any_raw = false;
   for (int c = 0; c < nc; c++) {
-    if (!raw[c].data) {
-      if (!encoded[c].data)
-        return fail(SN_ERR_BADARG, "column %d has neither raw nor encoded", c);
-      int32_t rc_pc = process_encoded_col(e, t, b, c, encoded[c]);
-      if (rc_pc != SN_OK) return rc_pc;
-      continue;
-    }
-    sn_type_t dt = t->schema[c].dtype;
-    int w, kind;
-    switch (dt) {
-      case SN_TYPE_DOUBLE: w = 8; kind = SN_K_F64; break;
-      case SN_TYPE_INT64:  w = 8; kind = SN_K_I64; break;
-      case SN_TYPE_INT32:  w = 4; kind = SN_K_I32; break;
-      case SN_TYPE_FLOAT:  w = 4; kind = SN_K_F32; break;
-      case SN_TYPE_INT16:  w = 2; kind = SN_K_I16; break;
-      default:
-        return fail(SN_ERR_UNSUPPORTED, "raw column %d dtype %d", c, (int)dt);
-    }
-    if (raw[c].len != (int64_t)num_rows * w)
-      return fail(SN_ERR_BADARG, "raw column %d length", c);
-    /* device blob = [typeId=0][nullBytes=0][body]: header at base+8
-     * (8-aligned), body at base+16 (16-aligned — arena blocks are
-     * 256-aligned); blob pointer = base+8, body_off = 8 */
-    char *base = (char *)e->arena.alloc((size_t)raw[c].len + 16);
-    if (!base) return fail(SN_ERR_NOMEM, "HBM upload failed");
-    char *body = base + 16;
-    b.cols[c].type_id = SN_ENC_UNCOMPRESSED;
-    if (e->arena.device >= 0) {
-      int32_t hdr[2] = { SN_ENC_UNCOMPRESSED, 0 };
-      if (hipMemcpy(base + 8, hdr, 8, hipMemcpyHostToDevice) != hipSuccess ||
-          h2d_copy(e, body, raw[c].data, (size_t)raw[c].len) != hipSuccess)
-        return fail(SN_ERR_NOMEM, "HBM upload failed");
-      if (sn_launch_col_minmax(body, num_rows, kind, sd + c, sd + nc + c,
-                               e->stream) != 0)
-        return fail(SN_ERR_GENERIC, "stats kernel");
-      b.is_raw[c] = 1;
-      any_raw = true;
-      b.col_dev[c] = base + 8;
-      b.cols[c].body_off = 8;
-      if (dt == SN_TYPE_DOUBLE &&
-          narrow_prefix_fits((const uint8_t *)raw[c].data, num_rows))
-        narrow_launch(e, t, b, c);
-    } else {
-      int32_t hdr[2] = { SN_ENC_UNCOMPRESSED, 0 };
-      memcpy(base + 8, hdr, 8);
-      memcpy(body, raw[c].data, (size_t)raw[c].len);
-      b.host_blobs.emplace_back((const uint8_t *)base + 8,
-                                (const uint8_t *)body + raw[c].len);
-      /* host-only: cheap scalar bounds so stats-skip still works */
-      b.lo_i.resize(nc); b.hi_i.resize(nc);
-      b.lo_d.resize(nc); b.hi_d.resize(nc);
-      b.null_count.resize(nc, 0);
-      b.bounds_null.resize(nc, 1);
-      const uint8_t *p8 = (const uint8_t *)raw[c].data;
-      if (dt == SN_TYPE_DOUBLE || dt == SN_TYPE_FLOAT) {
-        double mn = 0, mx = 0;
-        for (int32_t i = 0; i < num_rows; i++) {
-          double v = dt == SN_TYPE_DOUBLE ? rd_f64(p8 + (int64_t)i * 8)
-                                          : rd_f32(p8 + (int64_t)i * 4);
-          if (i == 0 || v < mn) mn = v;
-          if (i == 0 || v > mx) mx = v;
-        }
-        b.lo_d[c] = mn; b.hi_d[c] = mx;
-      } else {
-        int64_t mn = 0, mx = 0;
-        for (int32_t i = 0; i < num_rows; i++) {
-          int64_t v = w == 8 ? rd_i64(p8 + (int64_t)i * 8)
-                    : w == 4 ? rd_i32(p8 + (int64_t)i * 4)
-                             : rd_i16(p8 + (int64_t)i * 2);
-          if (i == 0 || v < mn) mn = v;
-          if (i == 0 || v > mx) mx = v;
-        }
-        b.lo_i[c] = mn; b.hi_i[c] = mx;
-      }
-      b.bounds_null[c] = 0;
-      b.stats_valid = true;
-    }
-    b.col_dev[c] = base + 8;
-    b.cols[c].body_off = 8;
+    if (!raw[c].data && !encoded[c].data)
+      return fail(SN_ERR_BADARG, "column %d has neither raw nor encoded", c);
+    int32_t rc = raw[c].data ? put_raw_col(e, t, b, c, raw[c], sd)
+                             : process_encoded_col(e, t, b, c, encoded[c]);
+    if (rc != SN_OK) return rc;
+    any_raw |= b.is_raw[c] != 0;
   }
   if (any_raw) {
     b.stats_dev = sd;
@@ -1750,24 +1505,7 @@ extern "C" int32_t sn_batch_put_raw(sn_engine *e, int32_t table,
   }
 
   std::lock_guard<std::mutex> g(t->mu);
-  for (int c = 0; c < nc; c++) {
-    if (t->schema[c].dtype != SN_TYPE_STRING || b.cols[c].dict.empty())
-      continue;
-    auto &l2g = b.cols[c].local2global;
-    l2g.reserve(b.cols[c].dict.size());
-    for (auto &sstr : b.cols[c].dict) {
-      auto it = t->gdict_idx[c].find(sstr);
-      int32_t gid;
-      if (it == t->gdict_idx[c].end()) {
-        gid = (int32_t)t->gdict[c].size();
-        t->gdict[c].push_back(sstr);
-        t->gdict_idx[c].emplace(sstr, gid);
-        if ((int32_t)sstr.size() > t->gdict_maxlen[c])
-          t->gdict_maxlen[c] = (int32_t)sstr.size();
-      } else gid = it->second;
-      l2g.push_back(gid);
-    }
-  }
+  intern_batch_dicts(t, b);
   t->total_rows += b.num_rows;
   t->batches.push_back(std::move(b));
   return SN_OK;
@@ -1804,10 +1542,7 @@ static void sync_pending_stats(sn_engine *e, Table *t) {
     if (hipMemcpy(h.data(), b.stats_dev, (size_t)nc * 16,
                   hipMemcpyDeviceToHost) != hipSuccess)
       continue;                         /* bounds stay absent: conservative */
-    b.lo_d.resize(nc); b.hi_d.resize(nc);
-    b.lo_i.resize(nc); b.hi_i.resize(nc);
-    b.null_count.assign(nc, 0);
-    b.bounds_null.assign(nc, 1);
+    alloc_bounds(b, nc);
     for (int c = 0; c < nc; c++) {
       if (!b.is_raw[c]) continue;
       sn_type_t dt = t->schema[c].dtype;
@@ -1839,60 +1574,28 @@ extern "C" int32_t sn_batch_put(sn_engine *e, int32_t table,
 
   const int nc = (int)t->schema.size();
   Batch b;
-  b.uuid = uuid; b.bucket = bucket_id;
+  batch_init(b, nc, uuid, bucket_id, num_rows < 0 ? -num_rows : num_rows);
   b.has_deltas = num_rows < 0;
-  b.num_rows = num_rows < 0 ? -num_rows : num_rows;
-  b.cols.resize(nc);
-  b.col_dev.resize(nc);
-  b.nullpfx_dev.resize(nc, nullptr);
-  b.patch_dev.resize(nc);
-  b.patch_host.resize(nc);
-  b.had_patches.assign(nc, 0);
-  b.rle_ends_dev.resize(nc, nullptr);
-  b.rle_vals_dev.resize(nc, nullptr);
-  b.rle_n.resize(nc, 0);
-  b.dictmap_cache.resize(nc);
-  b.narrow.resize(nc);
 
   /* Phase 1 — NO table lock: decompress, parse, validate, materialize and
    * upload are all batch-local (the arena has its own mutex), so concurrent
    * puts from many ingest threads overlap their heavy work.  Only the
-   * global-dictionary interning, delta decode (which interns) and the
+   * global-dictionary interning, the delta merge (which interns) and the
    * batches-vector append need t->mu (phase 2 below). */
-  for (int c = 0; c < nc; c++) {
-    int32_t rc_pc = process_encoded_col(e, t, b, c, columns[c]);
-    if (rc_pc != SN_OK) return rc_pc;
-  }
-
-
-  { int32_t rc_ = apply_delete_mask(e, b, delete_mask); if (rc_ != SN_OK) return rc_; }
-
+  int32_t rc = SN_OK;
+  for (int c = 0; c < nc && rc == SN_OK; c++)
+    rc = process_encoded_col(e, t, b, c, columns[c]);
+  if (rc != SN_OK) return rc;
+  if ((rc = apply_delete_mask(e, b, delete_mask)) != SN_OK) return rc;
   apply_stats(t, b, stats);
 
-  /* Phase 2 — under t->mu: global-dictionary interning, delta decode
-   * (interns new entries) and the append */
+  /* Phase 2 — under t->mu: global-dictionary interning, delta decode and
+   * merge (interns new entries) and the append */
   std::lock_guard<std::mutex> g(t->mu);
-  for (int c = 0; c < nc; c++) {
-    if (t->schema[c].dtype != SN_TYPE_STRING || b.cols[c].dict.empty())
-      continue;
-    auto &l2g = b.cols[c].local2global;
-    l2g.reserve(b.cols[c].dict.size());
-    for (auto &s : b.cols[c].dict) {
-      auto it = t->gdict_idx[c].find(s);
-      int32_t gid;
-      if (it == t->gdict_idx[c].end()) {
-        gid = (int32_t)t->gdict[c].size();
-        t->gdict[c].push_back(s);
-        t->gdict_idx[c].emplace(s, gid);
-        if ((int32_t)s.size() > t->gdict_maxlen[c])
-          t->gdict_maxlen[c] = (int32_t)s.size();
-      } else gid = it->second;
-      l2g.push_back(gid);
-    }
-  }
-
-  { int32_t rc_ = apply_deltas(e, t, b, deltas); if (rc_ != SN_OK) return rc_; }
-
+  ColDeltas dec;
+  if ((rc = decode_deltas(t, deltas, &dec)) != SN_OK) return rc;
+  intern_batch_dicts(t, b);
+  apply_deltas(e, t, b, deltas, dec);
   t->total_rows += b.num_rows;
   t->batches.push_back(std::move(b));
   return SN_OK;
@@ -1922,14 +1625,13 @@ extern "C" int32_t sn_batch_mutate(sn_engine *e, int32_t table, int64_t uuid,
     if (bb.uuid == uuid && bb.bucket == bucket_id) { b = &bb; break; }
   if (!b) return fail(SN_ERR_BADARG, "no batch uuid=%lld bucket=%d",
                       (long long)uuid, bucket_id);
-  if (delete_mask) {
-    int32_t rc = apply_delete_mask(e, *b, delete_mask);
-    if (rc != SN_OK) return rc;
-  }
-  if (deltas) {
-    int32_t rc = apply_deltas(e, t, *b, deltas);
-    if (rc != SN_OK) return rc;
-  }
+  /* decode before the first change, so a corrupt blob leaves the batch alone */
+  ColDeltas dec;
+  int32_t rc = decode_deltas(t, deltas, &dec);
+  if (rc != SN_OK) return rc;
+  if (delete_mask && (rc = apply_delete_mask(e, *b, delete_mask)) != SN_OK)
+    return rc;
+  apply_deltas(e, t, *b, deltas, dec);
   if (b->stats_pending) {
     /* caller-provided (or absent) stats supersede the device-computed ones */
     b->stats_pending = false;

@@ -24,6 +24,19 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "../../include/snappy_engine.h"
+
+/* bytes per value of a fixed-width column type; 0 for STRING */
+static inline int sn_type_width(sn_type_t dtype) {
+  switch (dtype) {
+    case SN_TYPE_DOUBLE: case SN_TYPE_INT64: return 8;
+    case SN_TYPE_INT32: case SN_TYPE_FLOAT: return 4;
+    case SN_TYPE_INT16: return 2;
+    case SN_TYPE_INT8: case SN_TYPE_BOOL: return 1;
+    default: return 0;
+  }
+}
+
 #define SN_DEV_MAX_COLS 8      /* referenced columns per plan */
 
 /* column value kinds as seen by the kernel */
