@@ -125,6 +125,16 @@ def main():
                                  aggs=[("sum", [(0, 0.0, 1.0)]), ("count", [])]))
     print("after UPDATE+DELETE:", qm.rows()[0][1])
 
+    # -- row-returning scan: SELECT v, ROWID WHERE v >= 5 LIMIT 4 ----------
+    rs = eng.select(abi.make_plan(table=tiny,
+                                  preds=[dict(col=0, is_double=True, lo=5.0)]),
+                    [0, abi.PROJ_ROWID], limit=4)
+    vals, valid = rs.column(0)
+    batches, ordinals = rs.rowids()
+    print(f"select: {rs.count()} of {rs.rows_passed()} matching rows:",
+          list(zip(vals.tolist(), batches.tolist(), ordinals.tolist())),
+          "batch 0 is", eng.batch_id(tiny, 0))
+
     eng.close()
 
 

@@ -492,6 +492,78 @@ int32_t   sn_dec_to_string(const sn_dec_val *v, char *buf, int32_t cap);
 /* sum / count at scale+4, rounded HALF_UP; NULL for a NULL sum, count <= 0
  * or a quotient of 10^38 or more */
 int32_t   sn_dec_avg(const sn_dec_val *sum, int64_t count, sn_dec_val *out);
+/* ---- row-returning filter scan: SELECT cols WHERE preds [LIMIT n] ----
+ * The ColumnTableScan -> Filter -> Project half of the operator surface
+ * (ColumnTableScan.scala:186-672 without an aggregate above it): what a host
+ * needs for plain SELECTs, for operators the engine does not run itself
+ * (non-colocated joins, sorts, windows), and for ColumnUpdateExec /
+ * ColumnDeleteExec, which need the batch and ordinal of every matching row
+ * to build the delta and delete blobs sn_batch_mutate accepts.
+ *
+ *   sn_scan_submit
+ *       — `plan` supplies table and predicates (every form sn_query_submit
+ *         takes: ranges, str_eq, IN-lists); plan->naggs and plan->ngroup must
+ *         be 0 (else SN_ERR_BADARG) and join_dim SN_JOIN_NONE (else
+ *         SN_ERR_UNSUPPORTED).  proj_cols[nproj], 1 <= nproj <= 8, are table
+ *         column ordinals or SN_PROJ_ROWID, duplicates allowed; predicate and
+ *         projected columns together may name at most 8 distinct table
+ *         columns (else SN_ERR_UNSUPPORTED).  limit <= 0: no limit.  Checks
+ *         run in the order: null arguments, unknown table, plan shape,
+ *         columns, then SN_ERR_NOGPU.
+ *         Rows come back in scan order — the table's batch order, then row
+ *         ordinal — the same from run to run; limit k keeps the first k rows
+ *         of that order.  Stats-based batch skipping applies.
+ *         The result is columnar and stays in device memory, owned by the
+ *         query and released at sn_query_destroy: projection p is a dense
+ *         array of sn_rows_count elements in the column's own type —
+ *         DOUBLE f64, INT64 i64, INT32 i32, FLOAT f32, INT16 i16, INT8 i8,
+ *         BOOL u8 0/1, STRING i32 global dictionary id (sn_table_dict_value),
+ *         ROWID i64 — plus one validity byte per row (1 value, 0 NULL; a NULL
+ *         row's value bytes are zero).  Values are copies, bit for bit: a
+ *         DOUBLE keeps its 64-bit pattern (-0.0, infinities, NaN payloads)
+ *         through plain bodies, 1-byte codes, run-length runs and update
+ *         deltas; INT64 is exact beyond 2^53.  (A FLOAT NaN stays a NaN; its
+ *         payload is not promised on batches with nulls or deltas.)
+ *         SN_PROJ_ROWID yields (batch << 32) | row ordinal, batch being the
+ *         table's own batch index — the one sn_table_get_blob takes, whatever
+ *         the scan skipped — which sn_table_batch_id turns into the
+ *         (uuid, bucket_id) of sn_batch_mutate.
+ *         On the handle: sn_query_wait/_destroy/_kernel_ms work (the time is
+ *         the sum of the three scan kernels' own intervals);
+ *         sn_query_result fills nrows = 0, naggs = 0 and the four metrics,
+ *         rows_passed being the matching rows BEFORE the limit;
+ *         sn_query_used_jit and sn_query_late_cols return 0;
+ *         sn_query_result_page, sn_query_order_by, sn_query_partials*,
+ *         sn_query_merge and sn_query_result_dec return SN_ERR_UNSUPPORTED.
+ *         A sharded engine returns its local rows; there is no exchange.
+ *   sn_rows_count
+ *       — rows returned (after the limit); waits for the query.
+ *   sn_rows_fetch
+ *       — copies rows [offset, offset + n) of projection `proj` to host
+ *         (dst_is_device 0) or HIP device memory (1): n elements to `values`,
+ *         n validity bytes to `valid` (may be NULL).  n == 0 is fine; a range
+ *         outside [0, count] is SN_ERR_BADARG.
+ *       Both return SN_ERR_BADARG on a handle from an aggregate submit.
+ *   sn_table_dict_value
+ *       — the bytes of global dictionary id `gid` of STRING column `col`:
+ *         returns the length and, when buf is not NULL, copies the value
+ *         (cap < length is SN_ERR_BADARG; a NUL follows when there is room).
+ *         A bad table, column or id is SN_ERR_BADARG.
+ *   sn_table_batch_id
+ *       — (uuid, bucket_id) of the table's batch `batch`, as given at put. */
+#define SN_PROJ_ROWID (-1)   /* pseudo-column: int64 (table batch index << 32)
+                                | row ordinal */
+sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
+                         int32_t nproj, const int32_t *proj_cols,
+                         int64_t limit);
+int64_t   sn_rows_count(sn_query *q);
+int32_t   sn_rows_fetch(sn_query *q, int32_t proj, int64_t offset, int64_t n,
+                        void *values, uint8_t *valid, int32_t dst_is_device);
+int32_t   sn_table_dict_value(sn_engine *e, int32_t table, int32_t col,
+                              int32_t gid, char *buf, int32_t cap);
+int32_t   sn_table_batch_id(sn_engine *e, int32_t table, int32_t batch,
+                            int64_t *uuid, int32_t *bucket);
+
 /* status code of the calling thread's last failure (pairs with
  * sn_last_error; lets callers of the pointer-returning submits tell
  * SN_ERR_UNSUPPORTED from SN_ERR_BADARG) */

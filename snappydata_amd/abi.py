@@ -16,7 +16,12 @@ T_INT32, T_INT64, T_DOUBLE, T_STRING, T_BOOL, T_INT16, T_INT8, T_FLOAT = range(8
 AGG_SUM, AGG_COUNT_STAR, AGG_AVG, AGG_MIN, AGG_MAX = range(5)
 
 OK = 0
+ERR_BADARG = -2
+ERR_UNSUPPORTED = -5
 ERR_NOGPU = -6
+
+PROJ_ROWID = -1          # SN_PROJ_ROWID: (table batch index << 32) | ordinal
+SN_SEL_MAX_PROJ = 8
 
 
 class SnBuf(C.Structure):

@@ -1776,10 +1776,30 @@ struct sn_query {
   int dec_scale_of[SN_MAX_AGGS];         /* result scale per logical agg */
   unsigned long long *dec_out = nullptr; /* device [nslots][sn_dec_row_cells] */
   std::vector<sn_dec_val> dec_vals;      /* host [nslots][plan.naggs] */
+  /* row-returning scan state (sn_scan_submit): the result stays on the
+   * device, one dense typed array and one validity array per projection */
+  bool select = false;
+  int sel_nproj = 0;
+  int32_t sel_cols[SN_SEL_MAX_PROJ];     /* table column or SN_PROJ_ROWID */
+  int64_t sel_limit = 0;
+  int64_t sel_total = 0;                 /* matching rows before the limit */
+  int64_t sel_rows = 0;                  /* rows returned */
+  int sel_width[SN_SEL_MAX_PROJ];        /* bytes per output element */
+  void *sel_val[SN_SEL_MAX_PROJ];
+  uint8_t *sel_valid[SN_SEL_MAX_PROJ];
+  int sel_kernels = 0;                   /* kernels launched: 0, 2 or 3 */
+  float sel_ms[3] = { 0.0f, 0.0f, 0.0f };  /* mark, offsets, gather */
+  hipEvent_t sel_ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr };    /* (start, stop) of mark, offsets, gather */
   ~sn_query() {
     if (e) { e->ev_release(ev_start); e->ev_release(ev_stop); ev_start = ev_stop = nullptr; }
     if (ev_start) (void)hipEventDestroy(ev_start);
     if (ev_stop) (void)hipEventDestroy(ev_stop);
+    for (hipEvent_t &ev : sel_ev) {
+      if (e) e->ev_release(ev);
+      else if (ev) (void)hipEventDestroy(ev);
+      ev = nullptr;
+    }
   }
 };
 
@@ -2321,6 +2341,9 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp,
   mix((uint64_t)t->batches.size());
   for (auto &c : t->gdict) mix(c.size() * 7919);
   mix(narrow_ok ? 0x6e617277ull : 0);
+  /* a row-returning scan's set (projection-only columns behind the predicate
+   * columns, no aggregate inputs, so no pac) is not an aggregate plan's */
+  if (q->select) mix(0x73656c656374ull + (uint64_t)plan->npreds);
 
   int64_t skip_count = 0;
   for (auto &b : t->batches)
@@ -3019,6 +3042,265 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
 }
 
 /* ================================================================== */
+/* row-returning filter scan: SELECT cols WHERE preds [LIMIT n]         */
+
+/* ---- select launch: mark -> tile offsets -> (host reads the total) ->
+ * gather.  dp.nused covers predicate and projection-only columns; pass 1
+ * stages the first npc (predicate) slots only.  The caller holds t->mu, so
+ * the scan-set -> table batch map sees the batches resolve_scan_set saw. ---- */
+static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
+                             const ScanSet &set, int npc) {
+  sn_engine *e = q->e;
+  const Table *t = q->t;
+  const int32_t ntiles = set.ntiles;
+  if (ntiles == 0) return SN_OK;
+  sn_dev_plan mp = dp;
+  mp.nused = npc;
+  void *mp_dev = cached_dev_plan(e, mp);
+  if (!mp_dev) return fail(SN_ERR_NOMEM, "plan upload");
+  /* engine scratch: [total][offsets ntiles][counts ntiles][bitmap], each
+   * region 256-byte aligned */
+  const size_t off_b = Arena::rnd((size_t)ntiles * 8);
+  const size_t cnt_b = Arena::rnd((size_t)ntiles * 4);
+  const size_t bm_b = (size_t)ntiles * SN_SEL_TILE_WORDS * 8;
+  int rc = ensure_scratch(e, 256 + off_b + cnt_b + bm_b);
+  if (rc != SN_OK) return rc;
+  uint8_t *base = (uint8_t *)e->scratch;
+  int64_t *total_dev = (int64_t *)base;
+  int64_t *offsets = (int64_t *)(base + 256);
+  int32_t *counts = (int32_t *)(base + 256 + off_b);
+  uint64_t *bitmap = (uint64_t *)(base + 256 + off_b + cnt_b);
+  for (hipEvent_t &ev : q->sel_ev) ev = e->ev_acquire();
+  if (hipMemsetAsync(counts, 0, (size_t)ntiles * 4, e->stream) != hipSuccess)
+    return fail(SN_ERR_GENERIC, "tile count zero");
+  if (q->sel_ev[0]) (void)hipEventRecord(q->sel_ev[0], e->stream);
+  rc = sn_launch_select_mark(&mp, (const sn_dev_plan *)mp_dev,
+                             (const sn_dev_batch *)set.db_dev,
+                             (const sn_dev_tile *)set.tl_dev, ntiles, bitmap,
+                             counts, e->stream);
+  if (q->sel_ev[1]) (void)hipEventRecord(q->sel_ev[1], e->stream);
+  if (rc != 0)
+    return fail(SN_ERR_GENERIC, "select mark launch: %s",
+                hipGetErrorString((hipError_t)rc));
+  if (q->sel_ev[2]) (void)hipEventRecord(q->sel_ev[2], e->stream);
+  rc = sn_launch_tile_offsets(counts, ntiles, offsets, total_dev, e->stream);
+  if (q->sel_ev[3]) (void)hipEventRecord(q->sel_ev[3], e->stream);
+  if (rc != 0)
+    return fail(SN_ERR_GENERIC, "tile offsets launch: %s",
+                hipGetErrorString((hipError_t)rc));
+  q->sel_kernels = 2;
+  /* the output is sized from the match count: one stream sync inside submit,
+   * as on the sparse route */
+  int64_t total = 0;
+  if (hipStreamSynchronize(e->stream) != hipSuccess ||
+      hipMemcpy(&total, total_dev, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(SN_ERR_GENERIC, "select count readback: %s",
+                hipGetErrorString(hipGetLastError()));
+  q->sel_total = total;
+  q->sel_rows = q->sel_limit > 0 ? std::min(total, q->sel_limit) : total;
+  if (q->sel_rows <= 0) return SN_OK;
+
+  sn_dev_select sel;
+  memset(&sel, 0, sizeof(sel));
+  sel.nproj = q->sel_nproj;
+  sel.out_rows = q->sel_rows;
+  for (int p = 0; p < q->sel_nproj; p++) {
+    const int32_t c = q->sel_cols[p];
+    sel.otype[p] = c == SN_PROJ_ROWID ? SN_SEL_ROWID : (int)t->schema[c].dtype;
+    sel.cslot[p] = c == SN_PROJ_ROWID ? 0 : q->cslot_of_col[c];
+    const size_t vb = (size_t)q->sel_rows * (size_t)q->sel_width[p];
+    const size_t nb = (size_t)q->sel_rows;
+    q->sel_val[p] = e->arena.alloc(vb);
+    if (q->sel_val[p]) q->owned.push_back({ q->sel_val[p], vb });
+    q->sel_valid[p] = (uint8_t *)e->arena.alloc(nb);
+    if (q->sel_valid[p]) q->owned.push_back({ q->sel_valid[p], nb });
+    if (!q->sel_val[p] || !q->sel_valid[p])
+      return fail(SN_ERR_NOMEM, "select output alloc (%lld rows)",
+                  (long long)q->sel_rows);
+    sel.val[p] = q->sel_val[p];
+    sel.valid[p] = q->sel_valid[p];
+  }
+  /* tile.batch indexes the scan set; ROWID names the table's own batch */
+  std::vector<int32_t> tb;
+  for (size_t bi = 0; bi < t->batches.size(); bi++)
+    if (!(q->batches_skipped && batch_skippable(t->batches[bi], &q->plan, t)))
+      tb.push_back((int32_t)bi);
+  const int32_t *tb_dev = (const int32_t *)up_owned(q, tb.data(), tb.size() * 4);
+  if (!tb_dev) return fail(SN_ERR_NOMEM, "batch map upload");
+  if (q->sel_ev[4]) (void)hipEventRecord(q->sel_ev[4], e->stream);
+  rc = sn_launch_select_gather(&sel, (const sn_dev_batch *)set.db_dev,
+                               (const sn_dev_tile *)set.tl_dev, ntiles, bitmap,
+                               counts, offsets, tb_dev, e->stream);
+  if (q->sel_ev[5]) (void)hipEventRecord(q->sel_ev[5], e->stream);
+  if (rc != 0)
+    return fail(SN_ERR_GENERIC, "select gather launch: %s",
+                hipGetErrorString((hipError_t)rc));
+  q->sel_kernels = 3;
+  return SN_OK;
+}
+
+extern "C" sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
+                                    int32_t nproj, const int32_t *proj_cols,
+                                    int64_t limit) {
+  if (!e || !plan || !proj_cols) {
+    fail(SN_ERR_BADARG, "null engine/plan/projection");
+    return nullptr;
+  }
+  Table *t = get_table(e, plan->table);
+  if (!t) { fail(SN_ERR_BADARG, "unknown table %d", plan->table); return nullptr; }
+  if (plan->naggs != 0 || plan->ngroup != 0) {
+    fail(SN_ERR_BADARG,
+         "a row-returning scan takes no aggregates and no group columns");
+    return nullptr;
+  }
+  if (plan->join_dim != SN_JOIN_NONE) {
+    fail(SN_ERR_UNSUPPORTED, "joins in row-returning scans are not supported");
+    return nullptr;
+  }
+  if (plan->npreds < 0 || plan->npreds > SN_MAX_PREDS) {
+    fail(SN_ERR_BADARG, "plan limits exceeded");
+    return nullptr;
+  }
+  if (nproj < 1 || nproj > SN_SEL_MAX_PROJ) {
+    fail(SN_ERR_BADARG, "nproj %d outside 1..%d", nproj, SN_SEL_MAX_PROJ);
+    return nullptr;
+  }
+  auto q = std::make_unique<sn_query>();
+  q->e = e; q->t = t; q->plan = *plan;
+  q->select = true;
+  q->sel_nproj = nproj;
+  q->sel_limit = limit > 0 ? limit : 0;
+  /* predicate columns take the first device slots, projection-only ones
+   * follow: pass 1 stages the former alone */
+  if (collect_plan_columns(q.get()) != SN_OK) return nullptr;
+  const int npc = (int)q->used_cols.size();
+  for (int p = 0; p < nproj; p++) {
+    const int32_t c = proj_cols[p];
+    q->sel_cols[p] = c;
+    if (c == SN_PROJ_ROWID) { q->sel_width[p] = 8; continue; }
+    if (c < 0 || c >= (int32_t)t->schema.size()) {
+      fail(SN_ERR_BADARG, "bad projection column %d", c);
+      return nullptr;
+    }
+    if (use_col(q.get(), c) < 0) {
+      fail(SN_ERR_UNSUPPORTED,
+           "predicates and projection name more than %d distinct columns",
+           SN_DEV_MAX_COLS);
+      return nullptr;
+    }
+    const sn_type_t dt = t->schema[c].dtype;
+    q->sel_width[p] = dt == SN_TYPE_STRING ? 4 : sn_type_width(dt);
+  }
+  if (!e->has_gpu) {
+    fail(SN_ERR_NOGPU, "no HIP device — the engine never falls back to CPU");
+    return nullptr;
+  }
+  std::lock_guard<std::mutex> qg(e->query_mu);
+  std::lock_guard<std::mutex> g(t->mu);
+  sync_pending_stats(e, t);
+  sn_dev_plan dp;
+  ScanSet set;
+  if (build_dev_plan(q.get(), false, dp) != SN_OK ||
+      resolve_scan_set(q.get(), dp, true, &set) != SN_OK ||
+      launch_select(q.get(), dp, set, npc) != SN_OK) {
+    /* a refused output allocation must not strand the blocks already taken
+     * (they can be large); nothing may still be reading them */
+    (void)hipStreamSynchronize(e->stream);
+    for (auto &pr : q->owned) e->arena.release(pr.first, pr.second);
+    return nullptr;
+  }
+  register_live(e, q.get());
+  return q.release();
+}
+
+static sn_query *rows_query(sn_query *q) {
+  if (!q) { fail(SN_ERR_BADARG, "null query"); return nullptr; }
+  if (!q->select) {
+    fail(SN_ERR_BADARG, "not a row-returning query (sn_scan_submit)");
+    return nullptr;
+  }
+  return q;
+}
+
+extern "C" int64_t sn_rows_count(sn_query *q) {
+  if (!rows_query(q)) return SN_ERR_BADARG;
+  int rc = sn_query_wait(q);
+  return rc != SN_OK ? rc : q->sel_rows;
+}
+
+/* measurement aid (not in the public header, like sn_engine_jit_count): the
+ * device intervals of k_select_mark, k_tile_offsets and k_select_gather, 0
+ * for a kernel that did not run; sn_query_kernel_ms is their sum */
+extern "C" int32_t sn_rows_kernel_ms(sn_query *q, double *ms3) {
+  if (!rows_query(q) || !ms3) return SN_ERR_BADARG;
+  int rc = sn_query_wait(q);
+  if (rc != SN_OK) return rc;
+  for (int i = 0; i < 3; i++) ms3[i] = (double)q->sel_ms[i];
+  return SN_OK;
+}
+
+extern "C" int32_t sn_rows_fetch(sn_query *q, int32_t proj, int64_t offset,
+                                 int64_t n, void *values, uint8_t *valid,
+                                 int32_t dst_is_device) {
+  if (!rows_query(q)) return SN_ERR_BADARG;
+  int rc = sn_query_wait(q);
+  if (rc != SN_OK) return rc;
+  if (proj < 0 || proj >= q->sel_nproj)
+    return fail(SN_ERR_BADARG, "projection %d out of range", proj);
+  if (offset < 0 || n < 0 || offset > q->sel_rows || n > q->sel_rows - offset)
+    return fail(SN_ERR_BADARG, "rows [%lld, %lld) outside [0, %lld]",
+                (long long)offset, (long long)(offset + n),
+                (long long)q->sel_rows);
+  if (n == 0) return SN_OK;
+  if (!values) return fail(SN_ERR_BADARG, "null values buffer");
+  const hipMemcpyKind kind =
+      dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t w = (size_t)q->sel_width[proj];
+  HIP_OR_FAIL(hipMemcpy(values, (const uint8_t *)q->sel_val[proj] +
+                                    (size_t)offset * w, (size_t)n * w, kind));
+  if (valid)
+    HIP_OR_FAIL(hipMemcpy(valid, q->sel_valid[proj] + offset, (size_t)n, kind));
+  return SN_OK;
+}
+
+extern "C" int32_t sn_table_dict_value(sn_engine *e, int32_t table,
+                                       int32_t col, int32_t gid, char *buf,
+                                       int32_t cap) {
+  if (!e) return fail(SN_ERR_BADARG, "null engine");
+  Table *t = get_table(e, table);
+  if (!t) return fail(SN_ERR_BADARG, "unknown table %d", table);
+  std::lock_guard<std::mutex> g(t->mu);
+  if (col < 0 || col >= (int32_t)t->schema.size() ||
+      t->schema[col].dtype != SN_TYPE_STRING)
+    return fail(SN_ERR_BADARG, "column %d is not a string column", col);
+  if (gid < 0 || (size_t)gid >= t->gdict[col].size())
+    return fail(SN_ERR_BADARG, "dictionary id %d out of range", gid);
+  const std::string &s = t->gdict[col][(size_t)gid];
+  if (buf) {
+    if (cap < 0 || (size_t)cap < s.size())
+      return fail(SN_ERR_BADARG, "buffer of %d bytes for a %zu-byte value",
+                  cap, s.size());
+    memcpy(buf, s.data(), s.size());
+    if ((size_t)cap > s.size()) buf[s.size()] = 0;
+  }
+  return (int32_t)s.size();
+}
+
+extern "C" int32_t sn_table_batch_id(sn_engine *e, int32_t table,
+                                     int32_t batch, int64_t *uuid,
+                                     int32_t *bucket) {
+  if (!e || !uuid || !bucket) return fail(SN_ERR_BADARG, "null argument");
+  Table *t = get_table(e, table);
+  if (!t) return fail(SN_ERR_BADARG, "unknown table %d", table);
+  std::lock_guard<std::mutex> g(t->mu);
+  if (batch < 0 || (size_t)batch >= t->batches.size())
+    return fail(SN_ERR_BADARG, "batch %d out of range", batch);
+  *uuid = t->batches[(size_t)batch].uuid;
+  *bucket = t->batches[(size_t)batch].bucket;
+  return SN_OK;
+}
+
+/* ================================================================== */
 /* exact DECIMAL aggregation: host side                                */
 
 typedef unsigned __int128 u128_t;
@@ -3284,6 +3566,10 @@ static void dec_finalize(sn_query *q, const unsigned long long *cells) {
 extern "C" int32_t sn_query_result_dec(sn_query *q, int64_t row, int32_t agg,
                                        sn_dec_val *out) {
   if (!q || !out) return fail(SN_ERR_BADARG, "null query/out");
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_result_dec is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (!q->dec) return fail(SN_ERR_BADARG, "not a decimal query");
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
@@ -3298,6 +3584,24 @@ extern "C" int32_t sn_query_result_dec(sn_query *q, int64_t row, int32_t agg,
 
 extern "C" int32_t sn_query_wait(sn_query *q) {
   if (!q) return SN_ERR_BADARG;
+  if (!q->done && q->select) {
+    /* the rows stay on the device (sn_rows_fetch); the duration is the sum
+     * of the three kernels' own intervals, without the host readback gap */
+    HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
+    float sum = 0.0f;
+    bool any = false;
+    for (int i = 0; i < 2 * q->sel_kernels; i += 2) {
+      float ms = 0.0f;
+      if (q->sel_ev[i] && q->sel_ev[i + 1] &&
+          hipEventElapsedTime(&ms, q->sel_ev[i], q->sel_ev[i + 1]) == hipSuccess) {
+        q->sel_ms[i / 2] = ms;
+        sum += ms;
+        any = true;
+      }
+    }
+    if (any) q->kernel_ms = sum;
+    q->done = true;
+  }
   if (!q->done && q->dec) {
     HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
     std::vector<unsigned long long> cells;
@@ -3514,6 +3818,18 @@ static int32_t result_fill_page(sn_query *q, int64_t offset, sn_result *out) {
 }
 
 extern "C" int32_t sn_query_result(sn_query *q, sn_result *out) {
+  if (q && q->select) {
+    /* no group rows: the metrics alone (the rows come from sn_rows_fetch) */
+    if (!out) return SN_ERR_BADARG;
+    int rc = sn_query_wait(q);
+    if (rc != SN_OK) return rc;
+    memset(out, 0, sizeof(*out));
+    out->rows_scanned = q->rows_scanned;
+    out->rows_passed = q->sel_total;
+    out->batches_seen = q->batches_seen;
+    out->batches_skipped = q->batches_skipped;
+    return SN_OK;
+  }
   return result_fill_page(q, 0, out);
 }
 
@@ -3521,6 +3837,10 @@ extern "C" int32_t sn_query_result(sn_query *q, sn_result *out) {
  * global-atomic grouped path): fills up to one page from `offset`. */
 extern "C" int32_t sn_query_result_page(sn_query *q, int64_t offset,
                                         sn_result *out) {
+  if (q && q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_result_page is not supported on a row-returning query "
+                "(its result is rows, read with sn_rows_fetch)");
   return result_fill_page(q, offset, out);
 }
 
@@ -3531,6 +3851,10 @@ extern "C" int32_t sn_query_result_page(sn_query *q, int64_t offset,
 extern "C" int32_t sn_query_order_by(sn_query *q, int32_t agg_idx,
                                      int32_t descending, int64_t k) {
   if (!q) return SN_ERR_BADARG;
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_order_by is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (q->dec)
     return fail(SN_ERR_UNSUPPORTED,
                 "sn_query_order_by is not supported on an exact decimal query (its "
@@ -3578,6 +3902,7 @@ extern "C" int32_t sn_query_order_by(sn_query *q, int32_t agg_idx,
 /* total group rows of the finalized result */
 extern "C" int64_t sn_query_num_groups(sn_query *q) {
   if (!q) return SN_ERR_BADARG;
+  if (q->select) return 0;
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
   if (q->final_groups.empty() && !q->merged) {
@@ -3632,6 +3957,10 @@ static int64_t partial_bytes_cap(sn_query *q, int32_t cap) {
 
 extern "C" int64_t sn_query_partial_bytes(sn_query *q) {
   if (!q) return SN_ERR_BADARG;
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partial_bytes is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (q->dec)
     return fail(SN_ERR_UNSUPPORTED,
                 "sn_query_partial_bytes is not supported on an exact decimal query (its "
@@ -3641,6 +3970,10 @@ extern "C" int64_t sn_query_partial_bytes(sn_query *q) {
 
 extern "C" int64_t sn_query_partial_bytes2(sn_query *q, int32_t cap_slots) {
   if (!q || cap_slots <= 0) return SN_ERR_BADARG;
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partial_bytes2 is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (q->dec)
     return fail(SN_ERR_UNSUPPORTED,
                 "sn_query_partial_bytes2 is not supported on an exact decimal query (its "
@@ -3651,6 +3984,10 @@ extern "C" int64_t sn_query_partial_bytes2(sn_query *q, int32_t cap_slots) {
 extern "C" int32_t sn_query_partials2(sn_query *q, void *dst,
                                       int32_t dst_is_device, int32_t cap_slots) {
   if (!q || !dst || cap_slots <= 0) return SN_ERR_BADARG;
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partials is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (q->dec)
     return fail(SN_ERR_UNSUPPORTED,
                 "sn_query_partials is not supported on an exact decimal query (its "
@@ -3714,6 +4051,10 @@ extern "C" int32_t sn_query_partials_sharded2(sn_query *q, int32_t world,
                                               void *dst, int32_t cap_slots) {
   if (!q || !dst || world <= 0 || world > 1024 || cap_slots <= 0)
     return SN_ERR_BADARG;
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_partials_sharded is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (q->dec)
     return fail(SN_ERR_UNSUPPORTED,
                 "sn_query_partials_sharded is not supported on an exact decimal query (its "
@@ -3768,6 +4109,10 @@ extern "C" int32_t sn_query_partials_sharded(sn_query *q, int32_t world,
 extern "C" int32_t sn_query_merge(sn_query *q, const void *blocks, int64_t stride,
                                   int32_t n_blocks) {
   if (!q || !blocks || n_blocks <= 0) return SN_ERR_BADARG;
+  if (q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "sn_query_merge is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)");
   if (q->dec)
     return fail(SN_ERR_UNSUPPORTED,
                 "sn_query_merge is not supported on an exact decimal query (its "

@@ -385,6 +385,11 @@ static inline SN_HD sn_lds sn_lds_dec(int nused, int nslots, int naggs) {
                        SN_LDS_SLACK_DEC);
 }
 
+/* row-returning scan, pass 1 (k_select_mark): the plan mirror only */
+static inline SN_HD sn_lds sn_lds_select(int nused) {
+  return sn_lds_layout(nused, 0, sizeof(sn_dev_plan), 0, 0);
+}
+
 /* does the grouped LDS-accumulator kernel fit, or must the plan take the
  * global-atomic route?  Asked by the launcher and by the engine, which must
  * zero the global accumulator before launch. */
@@ -522,6 +527,44 @@ int sn_launch_dec_scan(const sn_dev_plan *plan, const sn_dev_plan *dev_plan,
                        const sn_dev_tile *dev_tiles, int32_t ntiles,
                        unsigned long long *dev_out,
                        unsigned long long *dev_scratch, void *stream);
+
+/* ---- row-returning filter scan (sn_scan_submit): mark, offsets, gather ----
+ * Pass 1 leaves one alive bit per scanned row, tile-major: tile t owns the
+ * SN_SEL_TILE_WORDS 64-bit words from t * SN_SEL_TILE_WORDS, chunk c of the
+ * tile the SN_SCAN_CHUNK / 64 words from c * (SN_SCAN_CHUNK / 64); bit r of
+ * word w is row tile.row_start + c * SN_SCAN_CHUNK + w * 64 + r.  Words of
+ * chunks beyond the tile's last row are never written and never read. */
+#define SN_SEL_TILE_WORDS (SN_TILE_ROWS / 64)
+#define SN_SEL_MAX_PROJ 8
+#define SN_SEL_ROWID 8         /* otype of the ROWID pseudo-column (sn_type_t
+                                  values are 0..7) */
+typedef struct {
+  int32_t nproj, _p;
+  int64_t out_rows;            /* min(matching rows, limit): every store is
+                                  guarded by it */
+  int32_t cslot[SN_SEL_MAX_PROJ];   /* device column slot (unused for ROWID) */
+  int32_t otype[SN_SEL_MAX_PROJ];   /* sn_type_t of the output, or ROWID */
+  void *val[SN_SEL_MAX_PROJ];       /* dense typed output array */
+  uint8_t *valid[SN_SEL_MAX_PROJ];  /* one validity byte per output row */
+} sn_dev_select;
+
+/* pass 1: plan->nused must be the number of PREDICATE column slots (they come
+ * first in the descriptor set); counts[ntiles] zeroed by the caller */
+int sn_launch_select_mark(const sn_dev_plan *plan, const sn_dev_plan *dev_plan,
+                          const sn_dev_batch *dev_batches,
+                          const sn_dev_tile *dev_tiles, int32_t ntiles,
+                          uint64_t *bitmap, int32_t *counts, void *stream);
+/* offsets[i] = counts[0] + ... + counts[i-1] in 64 bits, *total = the sum;
+ * one workgroup, any n >= 0 */
+int sn_launch_tile_offsets(const int32_t *counts, int32_t n, int64_t *offsets,
+                           int64_t *total, void *stream);
+/* pass 2: table_batch[scan-set batch] = the table's own batch index */
+int sn_launch_select_gather(const sn_dev_select *sel,
+                            const sn_dev_batch *dev_batches,
+                            const sn_dev_tile *dev_tiles, int32_t ntiles,
+                            const uint64_t *bitmap, const int32_t *counts,
+                            const int64_t *offsets, const int32_t *table_batch,
+                            void *stream);
 
 /* put-time patch materialization into a null-free fixed-width device body */
 int sn_launch_patch_apply(void *body, const int32_t *pos, const double *val,

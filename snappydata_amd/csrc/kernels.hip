@@ -2883,3 +2883,256 @@ extern "C" int sn_launch_dec_scan(const sn_dev_plan *plan,
                      dev_scratch, grid, ns, dev_dec, dev_out);
   return (int)hipGetLastError();
 }
+
+/* ================= row-returning filter scan =================
+ * SELECT cols WHERE preds [LIMIT n]: the scan front end and the predicate
+ * sweeps of the aggregate kernels leave the per-chunk alive bitmap in LDS;
+ * pass 1 keeps it (1 bit per row, plus a match count per tile), a one-block
+ * scan turns the counts into output offsets, and pass 2 compacts each chunk's
+ * alive rows into an LDS list and copies the projected columns out densely.
+ * Row order is the scan order (tile, then row), so it is deterministic. */
+
+/* ---- pass 1: only the predicate columns (slots [0, plan.nused)) are staged ---- */
+template <int NC>
+__global__ __launch_bounds__(WG, 4)
+void k_select_mark(sn_dev_plan plan,
+                   const sn_dev_plan *__restrict__ plan_g,
+                   const sn_dev_batch *__restrict__ batches,
+                   const sn_dev_tile *__restrict__ tiles, int ntiles,
+                   uint64_t *__restrict__ bitmap, int32_t *__restrict__ counts) {
+  const int tid = threadIdx.x;
+  const int nused = plan.nused;
+  const int npd = plan.npreds_d, npi = plan.npreds_i;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const ScanLds S = scan_lds(smem, sn_lds_select(nused), plan_g);
+  __syncthreads();
+  /* scan_tiles hands the row phase no tile index: tiles start on multiples
+   * of SN_TILE_ROWS, so a chunk at such a base opens this block's next tile */
+  int t = (int)blockIdx.x - (int)gridDim.x;
+  scan_tiles<NC, 1>(batches, tiles, ntiles, nused, S, ROW_PHASE(=, &t) {
+      if ((base & (SN_TILE_ROWS - 1)) == 0) t += (int)gridDim.x;
+      alive_init(S.salive, S.sdead, rows, clean);
+      pred_sweeps(S.P, npd, npi, clean, S.sval, S.svalid, S.salive);
+      /* each wave stores the words it owns (alive_init's ownership rule) */
+      if ((tid & 63) == 0) {
+        uint64_t *dst = bitmap + (size_t)t * SN_SEL_TILE_WORDS +
+                        (size_t)((base & (SN_TILE_ROWS - 1)) / CHUNK) * (CHUNK / 64);
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < CHUNK / WG; k++) {
+          const int w = (tid + k * WG) >> 6;
+          const uint64_t aw = S.salive[w];
+          dst[w] = aw;
+          n += __popcll(aw);
+        }
+        if (n) (void)atomicAdd(&counts[t], n);
+      }
+  });
+}
+
+extern "C" int sn_launch_select_mark(const sn_dev_plan *plan,
+                                     const sn_dev_plan *dev_plan,
+                                     const sn_dev_batch *dev_batches,
+                                     const sn_dev_tile *dev_tiles,
+                                     int32_t ntiles, uint64_t *bitmap,
+                                     int32_t *counts, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ntiles <= 0 || plan->nused < 0 || plan->nused > SN_DEV_MAX_COLS)
+    return (int)hipErrorInvalidValue;
+  const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
+  const size_t lds = (size_t)sn_lds_select(plan->nused).total;
+  if (plan->nused <= 4)
+    hipLaunchKernelGGL((k_select_mark<4>), dim3(grid), dim3(WG), lds, s, *plan,
+                       dev_plan, dev_batches, dev_tiles, ntiles, bitmap, counts);
+  else
+    hipLaunchKernelGGL((k_select_mark<8>), dim3(grid), dim3(WG), lds, s, *plan,
+                       dev_plan, dev_batches, dev_tiles, ntiles, bitmap, counts);
+  return (int)hipGetLastError();
+}
+
+/* ---- exclusive scan of the tile counts: one block, WG counts per step with
+ * the running total carried from step to step ---- */
+__global__ __launch_bounds__(WG, 1)
+void k_tile_offsets(const int32_t *__restrict__ counts, int n,
+                    int64_t *__restrict__ offsets, int64_t *__restrict__ total) {
+  __shared__ long long wsum[WG / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  long long carry = 0;
+  for (int base = 0; base < n; base += WG) {
+    const int i = base + tid;
+    const long long v = i < n ? (long long)counts[i] : 0;
+    long long x = v;                       /* inclusive scan within the wave */
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const long long y = __shfl_up(x, off, 64);
+      if (lane >= off) x += y;
+    }
+    if (lane == 63) wsum[wid] = x;
+    __syncthreads();
+    long long before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < WG / 64; w++) {
+      const long long ws = wsum[w];
+      before += w < wid ? ws : 0;
+      all += ws;
+    }
+    if (i < n) offsets[i] = carry + before + x - v;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0) *total = carry;
+}
+
+extern "C" int sn_launch_tile_offsets(const int32_t *counts, int32_t n,
+                                      int64_t *offsets, int64_t *total,
+                                      void *stream) {
+  if (n < 0 || !total || (n > 0 && (!counts || !offsets)))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tile_offsets, dim3(1), dim3(WG), 0, (hipStream_t)stream,
+                     counts, n, offsets, total);
+  return (int)hipGetLastError();
+}
+
+/* ---- pass 2 ----
+ * one projected value of source row `row` to output row `o`.  Everything the
+ * switches test is uniform over the block (the batch's kind, the output
+ * type), so they are scalar branches.  Values are copied, never recomputed:
+ * f64 and f32 travel as their integer bit patterns. */
+__device__ __forceinline__ void select_emit(const sn_dev_col &c, int direct,
+                                            int otype, int row, void *val_,
+                                            uint8_t *valid, long long o) {
+  int ok = 1, gid = 0;
+  long long vi = 0;          /* integer value, or the f64 bit pattern */
+  unsigned fbits = 0;        /* f32 bit pattern */
+  int have = 0;
+  if (direct) {
+    have = 1;
+    switch (c.kind) {
+      case SN_K_F64: vi = as_global((const long long *)c.body)[row]; break;
+      case SN_K_F64C8:
+        vi = as_global((const long long *)c.rle_vals)
+            [as_global((const uint8_t *)c.body)[row]];
+        break;
+      case SN_K_I64: vi = as_global((const long long *)c.body)[row]; break;
+      case SN_K_I32: vi = as_global((const int32_t *)c.body)[row]; break;
+      case SN_K_F32: fbits = as_global((const unsigned *)c.body)[row]; break;
+      case SN_K_I16: vi = as_global((const int16_t *)c.body)[row]; break;
+      case SN_K_S8: vi = as_global((const int8_t *)c.body)[row]; break;
+      case SN_K_U8: vi = as_global((const uint8_t *)c.body)[row] == 1; break;
+      default: have = 0; break;
+    }
+  }
+  if (!have) {
+    double vd = 0.0;
+    ok = read_general(c, row, &vd, &vi, &gid);
+    if (otype == SN_TYPE_DOUBLE) vi = __double_as_longlong(vd);
+    else if (otype == SN_TYPE_FLOAT) fbits = __float_as_uint((float)vd);
+    else if (otype == SN_TYPE_STRING) vi = gid;
+    if (!ok) { vi = 0; fbits = 0; }
+  }
+  switch (otype) {
+    case SN_TYPE_DOUBLE: case SN_TYPE_INT64:
+      ((long long *)val_)[o] = vi; break;
+    case SN_TYPE_INT32: case SN_TYPE_STRING:
+      ((int32_t *)val_)[o] = (int32_t)vi; break;
+    case SN_TYPE_FLOAT: ((unsigned *)val_)[o] = fbits; break;
+    case SN_TYPE_INT16: ((int16_t *)val_)[o] = (int16_t)vi; break;
+    case SN_TYPE_INT8: ((int8_t *)val_)[o] = (int8_t)vi; break;
+    case SN_TYPE_BOOL: ((uint8_t *)val_)[o] = (uint8_t)(vi != 0); break;
+  }
+  valid[o] = (uint8_t)ok;
+}
+
+__global__ __launch_bounds__(WG, 4)
+void k_select_gather(sn_dev_select sel,
+                     const sn_dev_batch *__restrict__ batches,
+                     const sn_dev_tile *__restrict__ tiles, int ntiles,
+                     const uint64_t *__restrict__ bitmap,
+                     const int32_t *__restrict__ counts,
+                     const int64_t *__restrict__ offsets,
+                     const int32_t *__restrict__ table_batch) {
+  __shared__ uint64_t sword[CHUNK / 64];
+  __shared__ int spfx[CHUNK / 64 + 1];
+  __shared__ uint16_t slist[CHUNK];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long tile_off = offsets[t];
+    if (counts[t] == 0 || tile_off >= sel.out_rows) continue;   /* uniform */
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int num_rows = b.num_rows;
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, num_rows);
+    const int direct = b.clean;
+    const long long rowid_hi = (long long)table_batch[tile.batch] << 32;
+    const uint64_t *tw = bitmap + (size_t)t * SN_SEL_TILE_WORDS;
+    long long running = tile_off;
+    for (int base = tile.row_start; base < tile_end && running < sel.out_rows;
+         base += CHUNK) {
+      if (tid < CHUNK / 64)
+        sword[tid] = as_global(tw)[((base - tile.row_start) / CHUNK) *
+                                   (CHUNK / 64) + tid];
+      __syncthreads();
+      if (tid == 0) {
+        int acc = 0;
+        for (int w = 0; w < CHUNK / 64; w++) {
+          spfx[w] = acc;
+          acc += __popcll(sword[w]);
+        }
+        spfx[CHUNK / 64] = acc;
+      }
+      __syncthreads();
+      /* rank of an alive row = alive rows before it in the chunk */
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        const int r = tid + k * WG;
+        const uint64_t aw = sword[r >> 6];
+        if ((aw >> lane) & 1ull)
+          slist[spfx[r >> 6] + __popcll(aw & ((1ull << lane) - 1ull))] =
+              (uint16_t)r;
+      }
+      __syncthreads();
+      const int nalive = spfx[CHUNK / 64];
+      for (int p = 0; p < sel.nproj; p++) {
+        const int otype = sel.otype[p];
+        void *val = sel.val[p];
+        uint8_t *valid = sel.valid[p];
+        if (otype == SN_SEL_ROWID) {
+          for (int j = tid; j < nalive; j += WG) {
+            const long long o = running + j;
+            if (o >= sel.out_rows) break;
+            ((long long *)val)[o] = rowid_hi | (long long)(base + slist[j]);
+            valid[o] = 1;
+          }
+          continue;
+        }
+        const sn_dev_col &c = b.cols[sel.cslot[p]];
+        for (int j = tid; j < nalive; j += WG) {
+          const long long o = running + j;
+          const int row = base + slist[j];
+          if (o >= sel.out_rows || row >= num_rows) break;
+          select_emit(c, direct, otype, row, val, valid, o);
+        }
+      }
+      running += nalive;
+      __syncthreads();       /* slist and sword are rewritten next chunk */
+    }
+  }
+}
+
+extern "C" int sn_launch_select_gather(const sn_dev_select *sel,
+                                       const sn_dev_batch *dev_batches,
+                                       const sn_dev_tile *dev_tiles,
+                                       int32_t ntiles, const uint64_t *bitmap,
+                                       const int32_t *counts,
+                                       const int64_t *offsets,
+                                       const int32_t *table_batch,
+                                       void *stream) {
+  if (ntiles <= 0 || sel->nproj < 1 || sel->nproj > SN_SEL_MAX_PROJ ||
+      sel->out_rows <= 0)
+    return (int)hipErrorInvalidValue;
+  const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
+  hipLaunchKernelGGL(k_select_gather, dim3(grid), dim3(WG), 0,
+                     (hipStream_t)stream, *sel, dev_batches, dev_tiles, ntiles,
+                     bitmap, counts, offsets, table_batch);
+  return (int)hipGetLastError();
+}

@@ -169,6 +169,25 @@ def lib():
         L.sn_dec_avg.restype = C.c_int32
         L.sn_dec_avg.argtypes = [C.POINTER(abi.SnDecVal), C.c_int64,
                                  C.POINTER(abi.SnDecVal)]
+        L.sn_scan_submit.restype = C.c_void_p
+        L.sn_scan_submit.argtypes = [C.c_void_p, C.POINTER(abi.SnPlan),
+                                     C.c_int32, C.POINTER(C.c_int32),
+                                     C.c_int64]
+        L.sn_rows_count.restype = C.c_int64
+        L.sn_rows_count.argtypes = [C.c_void_p]
+        L.sn_rows_fetch.restype = C.c_int32
+        L.sn_rows_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int64,
+                                    C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_int32]
+        L.sn_rows_kernel_ms.restype = C.c_int32
+        L.sn_rows_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.sn_table_dict_value.restype = C.c_int32
+        L.sn_table_dict_value.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_char_p, C.c_int32]
+        L.sn_table_batch_id.restype = C.c_int32
+        L.sn_table_batch_id.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int32)]
         L.sn_gen_lineitem_arrays.argtypes = [
             C.c_int64, C.c_int32, C.c_int64,
             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -409,9 +428,73 @@ class Query:
             pass
 
 
+_ROW_DTYPE = {abi.T_DOUBLE: np.float64, abi.T_INT64: np.int64,
+              abi.T_INT32: np.int32, abi.T_FLOAT: np.float32,
+              abi.T_INT16: np.int16, abi.T_INT8: np.int8,
+              abi.T_BOOL: np.uint8, abi.T_STRING: np.int32}
+
+
+class RowSet(Query):
+    """Rows of Engine.select: columnar, resident on the device until fetched.
+    wait / kernel_ms / result (metrics only) / close work as on a Query; the
+    aggregate-result calls raise EngineError(SN_ERR_UNSUPPORTED)."""
+
+    def __init__(self, eng, handle, plan, table, cols, dtypes):
+        super().__init__(eng, handle, plan)
+        self.table = table
+        self.cols = list(cols)
+        self._dtypes = list(dtypes)      # numpy dtype per projection
+
+    def count(self):
+        """Rows returned (after the limit)."""
+        return _check(lib().sn_rows_count(self._h), "rows_count")
+
+    def kernel_ms_parts(self):
+        """(mark, tile offsets, gather) device intervals in ms; kernel_ms()
+        is their sum."""
+        ms = (C.c_double * 3)()
+        _check(lib().sn_rows_kernel_ms(self._h, ms), "rows_kernel_ms")
+        return tuple(ms)
+
+    def rows_passed(self):
+        """Rows matching the predicates, before the limit."""
+        return int(self.result().rows_passed)
+
+    def column(self, p, offset=0, n=None):
+        """(values in the column's own dtype, bool validity) of projection p.
+        STRING columns come back as int32 global dictionary ids (see
+        strings()), ROWID as int64."""
+        if n is None:
+            n = self.count() - offset
+        vals = np.zeros(max(n, 0), dtype=self._dtypes[p])
+        valid = np.zeros(max(n, 0), dtype=np.uint8)
+        _check(lib().sn_rows_fetch(self._h, p, offset, n, vals.ctypes.data,
+                                   valid.ctypes.data, 0), "rows_fetch")
+        return vals, valid.astype(bool)
+
+    def strings(self, p):
+        """Projection p of a STRING column as a list of bytes (None = NULL)."""
+        if self.cols[p] == abi.PROJ_ROWID or \
+                self._e._schemas[self.table][self.cols[p]][0] != abi.T_STRING:
+            raise EngineError(abi.ERR_BADARG, f"projection {p} is not a string")
+        gids, valid = self.column(p)
+        look = {int(g): self._e.dict_value(self.table, self.cols[p], int(g))
+                for g in np.unique(gids[valid])}
+        return [look[int(g)] if ok else None for g, ok in zip(gids, valid)]
+
+    def rowids(self, p=None):
+        """(table batch index, row ordinal) arrays of the ROWID projection
+        (the first one when p is None)."""
+        if p is None:
+            p = self.cols.index(abi.PROJ_ROWID)
+        v, _ = self.column(p)
+        return (v >> 32).astype(np.int64), (v & 0xFFFFFFFF).astype(np.int64)
+
+
 class Engine:
     def __init__(self, device=0, shard_rank=0, shard_count=1, n_buckets=0,
                  column_batch_size=0):
+        self._schemas = {}
         cfg = abi.SnConfig()
         cfg.device = device
         cfg.shard_rank = shard_rank
@@ -428,8 +511,10 @@ class Engine:
         for i, (dt, nl) in enumerate(schema):
             arr[i].dtype = dt
             arr[i].nullable = 1 if nl else 0
-        return _check(lib().sn_table_define(self._h, name.encode(), len(schema), arr),
-                      "table_define")
+        t = _check(lib().sn_table_define(self._h, name.encode(), len(schema), arr),
+                   "table_define")
+        self._schemas[t] = [(int(dt), bool(nl)) for dt, nl in schema]
+        return t
 
     def batch_put(self, table, uuid, bucket, num_rows, col_blobs,
                   stats=None, delete_mask=None, deltas=None):
@@ -571,6 +656,39 @@ class Engine:
         if not h:
             raise EngineError(-1, last_error())
         return Query(self, h, plan)
+
+    def select(self, plan, cols, limit=0):
+        """SELECT cols WHERE plan's predicates [LIMIT limit] (limit <= 0:
+        none): plan from abi.make_plan without aggregates or group columns,
+        cols = table column ordinals or abi.PROJ_ROWID.  Rows come back in
+        scan order (batch, then row ordinal).  Failures carry the engine's
+        status code."""
+        cols = [int(c) for c in cols]
+        arr = (C.c_int32 * max(len(cols), 1))(*cols)
+        h = lib().sn_scan_submit(self._h, C.byref(plan), len(cols), arr, limit)
+        if not h:
+            raise EngineError(lib().sn_last_error_code(), last_error())
+        schema = self._schemas.get(plan.table, [])
+        dtypes = [np.int64 if c == abi.PROJ_ROWID else _ROW_DTYPE[schema[c][0]]
+                  for c in cols]
+        return RowSet(self, h, plan, plan.table, cols, dtypes)
+
+    def dict_value(self, table, col, gid):
+        """bytes of global dictionary id `gid` of STRING column `col`."""
+        n = _check(lib().sn_table_dict_value(self._h, table, col, gid, None, 0),
+                   "dict_value")
+        buf = C.create_string_buffer(n + 1)
+        _check(lib().sn_table_dict_value(self._h, table, col, gid, buf, n + 1),
+               "dict_value")
+        return buf.raw[:n]
+
+    def batch_id(self, table, batch):
+        """(uuid, bucket) of the table's batch `batch` as given at put: the
+        arguments batch_mutate takes for the batch a ROWID names."""
+        uuid, bucket = C.c_int64(0), C.c_int32(0)
+        _check(lib().sn_table_batch_id(self._h, table, batch, C.byref(uuid),
+                                       C.byref(bucket)), "batch_id")
+        return int(uuid.value), int(bucket.value)
 
     def table_set_decimal(self, table, col, precision, scale):
         """Declare an INT64 column as DECIMAL(precision, scale) holding
