@@ -135,6 +135,15 @@ def main():
           list(zip(vals.tolist(), batches.tolist(), ordinals.tolist())),
           "batch 0 is", eng.batch_id(tiny, 0))
 
+    # -- ordered scan: SELECT v, ROWID WHERE v >= 1 ORDER BY v DESC LIMIT 3 --
+    rs = eng.select(abi.make_plan(table=tiny,
+                                  preds=[dict(col=0, is_double=True, lo=1.0)]),
+                    [0, abi.PROJ_ROWID], limit=3, order_by=0, descending=True)
+    vals, _ = rs.column(0)
+    _, ordinals = rs.rowids()
+    print(f"top {rs.count()} of {rs.rows_passed()} by v DESC:",
+          list(zip(vals.tolist(), ordinals.tolist())))
+
     eng.close()
 
 

@@ -564,6 +564,58 @@ int32_t   sn_table_dict_value(sn_engine *e, int32_t table, int32_t col,
 int32_t   sn_table_batch_id(sn_engine *e, int32_t table, int32_t batch,
                             int64_t *uuid, int32_t *bucket);
 
+/* ---- ordered row scan: SELECT cols WHERE preds ORDER BY key LIMIT k ----
+ * Spark's TakeOrderedAndProjectExec over ColumnTableScan -> Filter: the k
+ * rows with the smallest keys among the rows that pass the predicates, in
+ * key order, selected and sorted on the device.  The host never sees the
+ * other matching rows.
+ *
+ *   sn_scan_submit_ordered
+ *       — plan, nproj, proj_cols as in sn_scan_submit, validated the same way
+ *         in the same order; then
+ *           order_col: a table column ordinal (SN_PROJ_ROWID or an ordinal out
+ *             of range is SN_ERR_BADARG).  It need not be projected.  It
+ *             counts towards the 8 distinct device columns (a ninth is
+ *             SN_ERR_UNSUPPORTED);
+ *           order_flags: SN_ORDER_DESC, and at most one of
+ *             SN_ORDER_NULLS_FIRST / SN_ORDER_NULLS_LAST (any other bit, or
+ *             both NULLS bits, is SN_ERR_BADARG);
+ *           limit: 1 <= limit <= SN_ORDER_MAX_LIMIT.  limit < 1 is
+ *             SN_ERR_BADARG (an ordered scan without a limit is a full sort,
+ *             which this is not); a larger limit is SN_ERR_UNSUPPORTED;
+ *         then SN_ERR_NOGPU.
+ *         Ordering contract:
+ *           Key types — every column type can be the key.  INT8/16/32/64 sort
+ *             as signed integers (INT64 exact over its full range), BOOL false
+ *             < true, STRING by unsigned bytewise comparison of the values
+ *             (UTF8String's binary compare, not dictionary ids), FLOAT and
+ *             DOUBLE as Spark's nanSafeCompareDoubles: -0.0 equals 0.0, every
+ *             NaN equals every other NaN, and NaN is greater than +inf.
+ *           NULLs — Spark's default: NULLS FIRST ascending, NULLS LAST
+ *             descending; a NULLS flag overrides it.
+ *           Ties — rows whose keys compare equal (-0.0 and 0.0, NaNs of
+ *             different payloads, NULL and NULL included) come out in scan
+ *             order (table batch, then ordinal), ascending and descending
+ *             alike, so the result is a pure function of the table contents.
+ *           Values — projected values are copies with sn_scan_submit's
+ *             guarantees: a -0.0 key comes back as -0.0, NaN payloads survive.
+ *         The result is a rows handle like sn_scan_submit's: sn_rows_count is
+ *         min(matching rows, limit); sn_rows_fetch, sn_query_wait/_destroy/
+ *         _kernel_ms work (the time is mark + offsets + the order stage);
+ *         sn_query_result gives the metrics, rows_passed counted BEFORE the
+ *         limit; the other calls return SN_ERR_UNSUPPORTED as on an unordered
+ *         rows handle.
+ *         A sharded engine returns its LOCAL top k; merging the shards' sorted
+ *         locals (a k-way merge of at most k rows each) is the host's job. */
+#define SN_ORDER_DESC         1
+#define SN_ORDER_NULLS_FIRST  2   /* explicit; at most one of the two */
+#define SN_ORDER_NULLS_LAST   4
+#define SN_ORDER_MAX_LIMIT    8192
+sn_query *sn_scan_submit_ordered(sn_engine *e, const sn_plan *plan,
+                                 int32_t nproj, const int32_t *proj_cols,
+                                 int32_t order_col, int32_t order_flags,
+                                 int64_t limit);
+
 /* status code of the calling thread's last failure (pairs with
  * sn_last_error; lets callers of the pointer-returning submits tell
  * SN_ERR_UNSUPPORTED from SN_ERR_BADARG) */

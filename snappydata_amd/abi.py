@@ -22,6 +22,9 @@ ERR_NOGPU = -6
 
 PROJ_ROWID = -1          # SN_PROJ_ROWID: (table batch index << 32) | ordinal
 SN_SEL_MAX_PROJ = 8
+# sn_scan_submit_ordered: order_flags bits and the largest limit
+ORDER_DESC, ORDER_NULLS_FIRST, ORDER_NULLS_LAST = 1, 2, 4
+ORDER_MAX_LIMIT = 8192
 
 
 class SnBuf(C.Structure):

@@ -236,6 +236,9 @@ struct Table {
    * bytes cannot travel in results/partial blocks — queries grouping on
    * such a column fail loudly instead of silently merging truncated keys */
   std::vector<int32_t> gdict_maxlen;
+  /* ORDER BY on a string column: global dictionary id -> bytewise rank,
+   * built on first use and rebuilt when the dictionary has grown */
+  std::map<int32_t, std::vector<int32_t>> order_ranks;
   /* last adequate sparse hash-table capacity (log2): later queries start
    * there instead of rediscovering it through grow-and-retry */
   int sparse_cap_hint = 0;
@@ -1788,6 +1791,10 @@ struct sn_query {
   void *sel_val[SN_SEL_MAX_PROJ];
   uint8_t *sel_valid[SN_SEL_MAX_PROJ];
   int sel_kernels = 0;                   /* kernels launched: 0, 2 or 3 */
+  /* ordered scan (sn_scan_submit_ordered): the third interval is the whole
+   * order stage, select to gather */
+  bool ordered = false;
+  int32_t ord_col = 0, ord_flags = 0;
   float sel_ms[3] = { 0.0f, 0.0f, 0.0f };  /* mark, offsets, gather */
   hipEvent_t sel_ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr,
                            nullptr };    /* (start, stop) of mark, offsets, gather */
@@ -3044,6 +3051,119 @@ extern "C" sn_query *sn_query_submit(sn_engine *e, const sn_plan *plan) {
 /* ================================================================== */
 /* row-returning filter scan: SELECT cols WHERE preds [LIMIT n]         */
 
+/* ---- ORDER BY on a string key: ranks[gid] = position of value gid among the
+ * values sorted by unsigned bytewise comparison (a shorter value sorts before
+ * its extensions).  Interned values are distinct, so rank is a bijection. */
+static void order_ranks_of(const std::vector<std::pair<const char *, size_t>> &v,
+                           int32_t *ranks) {
+  std::vector<int32_t> idx(v.size());
+  for (size_t i = 0; i < idx.size(); i++) idx[i] = (int32_t)i;
+  std::sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) {
+    const size_t la = v[(size_t)a].second, lb = v[(size_t)b].second;
+    const size_t m = std::min(la, lb);
+    const int c = m ? memcmp(v[(size_t)a].first, v[(size_t)b].first, m) : 0;
+    if (c != 0) return c < 0;
+    if (la != lb) return la < lb;
+    return a < b;                /* equal values (the exported builder only) */
+  });
+  for (size_t r = 0; r < idx.size(); r++) ranks[(size_t)idx[r]] = (int32_t)r;
+}
+
+/* test aid (not in the public header, like sn_rows_kernel_ms): the rank table
+ * of n values, value i = bytes [offsets[i], offsets[i + 1]) */
+extern "C" int32_t sn_order_dict_ranks(int32_t n, const uint8_t *bytes,
+                                       const int64_t *offsets, int32_t *ranks) {
+  if (n < 0 || (n > 0 && (!offsets || !ranks)))
+    return fail(SN_ERR_BADARG, "null argument");
+  std::vector<std::pair<const char *, size_t>> v((size_t)n);
+  for (int32_t i = 0; i < n; i++) {
+    if (offsets[i] < 0 || offsets[i + 1] < offsets[i] ||
+        (offsets[i + 1] > offsets[i] && !bytes))
+      return fail(SN_ERR_BADARG, "bad offsets at value %d", i);
+    v[(size_t)i] = { (const char *)bytes + offsets[i],
+                     (size_t)(offsets[i + 1] - offsets[i]) };
+  }
+  order_ranks_of(v, ranks);
+  return SN_OK;
+}
+
+/* test aid: the device's key image of a non-NULL value, computed on the host.
+ * bits: the integer value sign-extended to 64 bits, a DOUBLE's bit pattern, a
+ * FLOAT's in the low 32 bits, a STRING's rank, a BOOL as 0/1. */
+extern "C" uint64_t sn_order_key_h(int32_t dtype, uint64_t bits, int32_t desc) {
+  return sn_order_image(dtype, (long long)bits, (unsigned)bits, desc != 0);
+}
+
+/* the table's cached rank table for string column c (caller holds t->mu) */
+static const std::vector<int32_t> &table_order_ranks(Table *t, int32_t c) {
+  std::vector<int32_t> &r = t->order_ranks[c];
+  const std::vector<std::string> &d = t->gdict[(size_t)c];
+  if (r.size() != d.size()) {
+    std::vector<std::pair<const char *, size_t>> v(d.size());
+    for (size_t i = 0; i < d.size(); i++) v[i] = { d[i].data(), d[i].size() };
+    r.assign(d.size(), 0);
+    order_ranks_of(v, r.data());
+  }
+  return r;
+}
+
+/* ---- the order stage of an ordered scan, after launch_select has read the
+ * total and allocated q->sel_rows output rows: radix select, tie quota,
+ * sort, ordered gather — all on the stream, bracketed by one event pair ---- */
+static int32_t launch_order_stage(sn_query *q, const ScanSet &set,
+                                  uint8_t *ord_base, size_t zero_b,
+                                  size_t off_b, const uint64_t *bitmap,
+                                  const int32_t *counts,
+                                  const sn_dev_select &sel,
+                                  const int32_t *tb_dev) {
+  sn_engine *e = q->e;
+  Table *t = q->t;
+  const int32_t ntiles = set.ntiles;
+  const sn_type_t dt = t->schema[(size_t)q->ord_col].dtype;
+  sn_dev_order od;
+  memset(&od, 0, sizeof(od));
+  od.cslot = q->cslot_of_col[q->ord_col];
+  od.dtype = (int32_t)dt;
+  od.desc = (q->ord_flags & SN_ORDER_DESC) ? 1 : 0;
+  const bool nulls_first = (q->ord_flags & SN_ORDER_NULLS_FIRST) ? true
+      : (q->ord_flags & SN_ORDER_NULLS_LAST) ? false : !od.desc;
+  od.null_cls = nulls_first ? SN_ORD_CLS_FIRST : SN_ORD_CLS_LAST;
+  od.npass = sn_order_passes((int)dt);
+  if (dt == SN_TYPE_STRING) {
+    const std::vector<int32_t> &r = table_order_ranks(t, q->ord_col);
+    od.nranks = (int32_t)r.size();
+    if (!r.empty()) {
+      od.ranks = (const int32_t *)up_owned(q, r.data(), r.size() * 4);
+      if (!od.ranks) return fail(SN_ERR_NOMEM, "rank table upload");
+    }
+  }
+  sn_order_state *state = (sn_order_state *)ord_base;
+  unsigned long long *hist = (unsigned long long *)(ord_base + 256);
+  int32_t *eq_counts = (int32_t *)(ord_base + 256 +
+                                   (size_t)SN_ORD_MAX_PASSES * SN_ORD_HIST * 8);
+  int64_t *eq_offsets = (int64_t *)(ord_base + zero_b);
+  int64_t *eq_total = (int64_t *)(ord_base + zero_b + off_b);
+  sn_order_ent *cand = (sn_order_ent *)(ord_base + zero_b + off_b + 256);
+  if (q->sel_ev[4]) (void)hipEventRecord(q->sel_ev[4], e->stream);
+  if (hipMemsetAsync(ord_base, 0, zero_b, e->stream) != hipSuccess)
+    return fail(SN_ERR_GENERIC, "order state zero");
+  int rc = sn_launch_order_select(&od, (const sn_dev_batch *)set.db_dev,
+                                  (const sn_dev_tile *)set.tl_dev, ntiles,
+                                  bitmap, counts, state, hist, eq_counts,
+                                  eq_offsets, eq_total, cand,
+                                  (int32_t)q->sel_rows, e->stream);
+  if (rc == 0) rc = sn_launch_order_sort(cand, (int32_t)q->sel_rows, e->stream);
+  if (rc == 0)
+    rc = sn_launch_order_gather(&sel, (const sn_dev_batch *)set.db_dev, cand,
+                                tb_dev, e->stream);
+  if (q->sel_ev[5]) (void)hipEventRecord(q->sel_ev[5], e->stream);
+  if (rc != 0)
+    return fail(SN_ERR_GENERIC, "order stage launch: %s",
+                hipGetErrorString((hipError_t)rc));
+  q->sel_kernels = 3;
+  return SN_OK;
+}
+
 /* ---- select launch: mark -> tile offsets -> (host reads the total) ->
  * gather.  dp.nused covers predicate and projection-only columns; pass 1
  * stages the first npc (predicate) slots only.  The caller holds t->mu, so
@@ -3062,10 +3182,18 @@ static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
    * region 256-byte aligned */
   const size_t off_b = Arena::rnd((size_t)ntiles * 8);
   const size_t cnt_b = Arena::rnd((size_t)ntiles * 4);
-  const size_t bm_b = (size_t)ntiles * SN_SEL_TILE_WORDS * 8;
-  int rc = ensure_scratch(e, 256 + off_b + cnt_b + bm_b);
+  const size_t bm_b = Arena::rnd((size_t)ntiles * SN_SEL_TILE_WORDS * 8);
+  /* an ordered scan appends [state + histograms + equal counts] (zeroed by
+   * one memset) [equal offsets][equal total][candidates] */
+  const size_t ord_zero_b = Arena::rnd(
+      256 + (size_t)SN_ORD_MAX_PASSES * SN_ORD_HIST * 8 + (size_t)ntiles * 4);
+  const size_t ord_b = !q->ordered ? 0
+      : ord_zero_b + off_b + 256 +
+        (size_t)SN_ORDER_MAX_LIMIT * sizeof(sn_order_ent);
+  int rc = ensure_scratch(e, 256 + off_b + cnt_b + bm_b + ord_b);
   if (rc != SN_OK) return rc;
   uint8_t *base = (uint8_t *)e->scratch;
+  uint8_t *ord_base = base + 256 + off_b + cnt_b + bm_b;
   int64_t *total_dev = (int64_t *)base;
   int64_t *offsets = (int64_t *)(base + 256);
   int32_t *counts = (int32_t *)(base + 256 + off_b);
@@ -3127,6 +3255,9 @@ static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
       tb.push_back((int32_t)bi);
   const int32_t *tb_dev = (const int32_t *)up_owned(q, tb.data(), tb.size() * 4);
   if (!tb_dev) return fail(SN_ERR_NOMEM, "batch map upload");
+  if (q->ordered)
+    return launch_order_stage(q, set, ord_base, ord_zero_b, off_b, bitmap,
+                              counts, sel, tb_dev);
   if (q->sel_ev[4]) (void)hipEventRecord(q->sel_ev[4], e->stream);
   rc = sn_launch_select_gather(&sel, (const sn_dev_batch *)set.db_dev,
                                (const sn_dev_tile *)set.tl_dev, ntiles, bitmap,
@@ -3139,9 +3270,12 @@ static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
   return SN_OK;
 }
 
-extern "C" sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
-                                    int32_t nproj, const int32_t *proj_cols,
-                                    int64_t limit) {
+/* ORDER BY request of sn_scan_submit_ordered */
+struct OrderReq { int32_t col, flags; };
+
+static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
+                                  int32_t nproj, const int32_t *proj_cols,
+                                  int64_t limit, const OrderReq *ord) {
   if (!e || !plan || !proj_cols) {
     fail(SN_ERR_BADARG, "null engine/plan/projection");
     return nullptr;
@@ -3191,6 +3325,39 @@ extern "C" sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
     const sn_type_t dt = t->schema[c].dtype;
     q->sel_width[p] = dt == SN_TYPE_STRING ? 4 : sn_type_width(dt);
   }
+  if (ord) {
+    if (ord->col < 0 || ord->col >= (int32_t)t->schema.size()) {
+      fail(SN_ERR_BADARG, "bad order column %d", ord->col);
+      return nullptr;
+    }
+    const int32_t known =
+        SN_ORDER_DESC | SN_ORDER_NULLS_FIRST | SN_ORDER_NULLS_LAST;
+    if ((ord->flags & ~known) ||
+        ((ord->flags & SN_ORDER_NULLS_FIRST) &&
+         (ord->flags & SN_ORDER_NULLS_LAST))) {
+      fail(SN_ERR_BADARG, "bad order flags 0x%x", (unsigned)ord->flags);
+      return nullptr;
+    }
+    if (limit < 1) {
+      fail(SN_ERR_BADARG, "an ordered scan needs a limit of at least 1 "
+                          "(no limit would be a full sort)");
+      return nullptr;
+    }
+    if (limit > SN_ORDER_MAX_LIMIT) {
+      fail(SN_ERR_UNSUPPORTED, "ordered scan limit %lld beyond %d",
+           (long long)limit, SN_ORDER_MAX_LIMIT);
+      return nullptr;
+    }
+    if (use_col(q.get(), ord->col) < 0) {
+      fail(SN_ERR_UNSUPPORTED,
+           "predicates, projection and order key name more than %d distinct "
+           "columns", SN_DEV_MAX_COLS);
+      return nullptr;
+    }
+    q->ordered = true;
+    q->ord_col = ord->col;
+    q->ord_flags = ord->flags;
+  }
   if (!e->has_gpu) {
     fail(SN_ERR_NOGPU, "no HIP device — the engine never falls back to CPU");
     return nullptr;
@@ -3213,6 +3380,22 @@ extern "C" sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
   return q.release();
 }
 
+extern "C" sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
+                                    int32_t nproj, const int32_t *proj_cols,
+                                    int64_t limit) {
+  return scan_submit_impl(e, plan, nproj, proj_cols, limit, nullptr);
+}
+
+extern "C" sn_query *sn_scan_submit_ordered(sn_engine *e, const sn_plan *plan,
+                                            int32_t nproj,
+                                            const int32_t *proj_cols,
+                                            int32_t order_col,
+                                            int32_t order_flags,
+                                            int64_t limit) {
+  const OrderReq ord = { order_col, order_flags };
+  return scan_submit_impl(e, plan, nproj, proj_cols, limit, &ord);
+}
+
 static sn_query *rows_query(sn_query *q) {
   if (!q) { fail(SN_ERR_BADARG, "null query"); return nullptr; }
   if (!q->select) {
@@ -3230,7 +3413,8 @@ extern "C" int64_t sn_rows_count(sn_query *q) {
 
 /* measurement aid (not in the public header, like sn_engine_jit_count): the
  * device intervals of k_select_mark, k_tile_offsets and k_select_gather, 0
- * for a kernel that did not run; sn_query_kernel_ms is their sum */
+ * for a kernel that did not run; sn_query_kernel_ms is their sum.  On an
+ * ordered handle the third is the whole order stage (one event pair). */
 extern "C" int32_t sn_rows_kernel_ms(sn_query *q, double *ms3) {
   if (!rows_query(q) || !ms3) return SN_ERR_BADARG;
   int rc = sn_query_wait(q);

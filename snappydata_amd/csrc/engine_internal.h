@@ -566,6 +566,127 @@ int sn_launch_select_gather(const sn_dev_select *sel,
                             const int64_t *offsets, const int32_t *table_batch,
                             void *stream);
 
+/* ---- ordered row scan (sn_scan_submit_ordered): ORDER BY key LIMIT k ----
+ * After mark + offsets, a radix select over the alive rows' key images finds
+ * the k-th smallest (the threshold T), a quota pass takes the rows below T
+ * and the first `need` rows equal to T in scan order, one workgroup sorts the
+ * k candidates and a gather projects them in that order.
+ *
+ * Key image: (class, u64).  class orders NULLs against values — NULLS FIRST
+ * rows are class 0, values class 1, NULLS LAST rows class 2 — and the u64 is
+ * an order-preserving map of the value, complemented for DESC; a NULL's u64
+ * is 0.  Images compare as (class, u64); rows whose images are equal keep
+ * their scan order. */
+#define SN_ORD_DIGIT_BITS 11
+#define SN_ORD_BINS (1 << SN_ORD_DIGIT_BITS)
+/* one pass's histogram: [0] the NULLS FIRST class, [1 + d] digit d,
+ * [SN_ORD_BINS + 1] the NULLS LAST class — bin order is image order */
+#define SN_ORD_HIST (SN_ORD_BINS + 2)
+#define SN_ORD_MAX_PASSES 6
+#define SN_ORD_CLS_FIRST 0
+#define SN_ORD_CLS_VALUE 1
+#define SN_ORD_CLS_LAST 2
+#define SN_ORD_CLS_PAD 3       /* k_order_sort's padding, above everything */
+#define SN_ORD_POS_MASK 0x3fffffffffffffffull
+
+/* a candidate row: cp = class << 62 | scan-set batch << 32 | row ordinal
+ * (batch < 2^30, row < 2^31), so entries order as (cp >> 62, key, cp) */
+typedef struct { uint64_t key; uint64_t cp; } sn_order_ent;
+
+/* device state of one ordered scan: k_order_pick extends `prefix` by a digit
+ * per pass and lowers `need` to the rank wanted inside the chosen bin; after
+ * the last pass (cls, prefix) is T and need the quota of rows equal to T */
+typedef struct {
+  uint64_t prefix;
+  int64_t need;
+  int32_t cls;                 /* class of T, fixed by pass 0 */
+  int32_t cursor;              /* candidates appended so far */
+} sn_order_state;
+
+typedef struct {
+  int32_t cslot;               /* device column slot of the key */
+  int32_t dtype;               /* sn_type_t of the key column */
+  int32_t desc;
+  int32_t null_cls;            /* SN_ORD_CLS_FIRST or SN_ORD_CLS_LAST */
+  int32_t npass;               /* ceil(key bits / 11) */
+  int32_t nranks;              /* STRING: entries of ranks */
+  const int32_t *ranks;        /* STRING: global dictionary id -> bytewise rank */
+} sn_dev_order;
+
+static inline SN_HD int sn_order_key_bits(int dtype) {
+  switch (dtype) {
+    case SN_TYPE_DOUBLE: case SN_TYPE_INT64: return 64;
+    case SN_TYPE_INT32: case SN_TYPE_FLOAT: case SN_TYPE_STRING: return 32;
+    case SN_TYPE_INT16: return 16;
+    case SN_TYPE_INT8: return 8;
+    default: return 1;         /* BOOL */
+  }
+}
+static inline SN_HD int sn_order_passes(int dtype) {
+  return (sn_order_key_bits(dtype) + SN_ORD_DIGIT_BITS - 1) / SN_ORD_DIGIT_BITS;
+}
+
+/* the u64 of a non-NULL key.  vi: the integer value (sign-extended), the f64
+ * bit pattern, the STRING's rank or the BOOL as 0/1; fbits: the f32 pattern.
+ * Floats order as Spark's nanSafeCompare: -0.0 folds to 0.0 and every NaN to
+ * one pattern above +inf, then the sn_f64_ord map.  Integers get a sign bias.
+ * DESC complements within the key width. */
+static inline SN_HD unsigned long long sn_order_image(int dtype, long long vi,
+                                                      unsigned fbits, int desc) {
+  unsigned long long k;
+  switch (dtype) {
+    case SN_TYPE_DOUBLE: {
+      unsigned long long b = (unsigned long long)vi;
+      if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull)
+        b = 0x7ff8000000000000ull;
+      else if (b == 0x8000000000000000ull) b = 0;
+      k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+      break;
+    }
+    case SN_TYPE_FLOAT: {
+      unsigned b = fbits;
+      if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;
+      else if (b == 0x80000000u) b = 0;
+      k = (b >> 31) ? (unsigned)~b : (b | 0x80000000u);
+      break;
+    }
+    case SN_TYPE_INT64: k = (unsigned long long)vi ^ 0x8000000000000000ull; break;
+    case SN_TYPE_INT32: k = (unsigned)(int32_t)vi ^ 0x80000000u; break;
+    case SN_TYPE_STRING: k = (unsigned)(int32_t)vi; break;
+    case SN_TYPE_INT16: k = (unsigned)((uint16_t)(int16_t)vi ^ 0x8000u); break;
+    case SN_TYPE_INT8: k = (unsigned)((uint8_t)(int8_t)vi ^ 0x80u); break;
+    default: k = vi != 0; break;
+  }
+  if (desc) {
+    const int bits = sn_order_key_bits(dtype);
+    k ^= bits == 64 ? ~0ull : ((1ull << bits) - 1ull);
+  }
+  return k;
+}
+
+/* the whole order stage but the sort and the gather, on `stream` with no host
+ * sync: npass x (k_order_hist, k_order_pick), k_order_count, k_tile_offsets
+ * over the equal counts, k_order_collect.  bitmap / counts are pass 1's.
+ * The caller zeroes state, hist [npass][SN_ORD_HIST] and eq_counts [ntiles];
+ * cand holds k_eff entries, 1 <= k_eff <= min(alive rows, SN_ORDER_MAX_LIMIT),
+ * and is filled completely, in no particular order. */
+int sn_launch_order_select(const sn_dev_order *od,
+                           const sn_dev_batch *dev_batches,
+                           const sn_dev_tile *dev_tiles, int32_t ntiles,
+                           const uint64_t *bitmap, const int32_t *counts,
+                           sn_order_state *state, unsigned long long *hist,
+                           int32_t *eq_counts, int64_t *eq_offsets,
+                           int64_t *eq_total, sn_order_ent *cand,
+                           int32_t k_eff, void *stream);
+/* sorts ents[0, n) in place by (class, key, position), 0 <= n <=
+ * SN_ORDER_MAX_LIMIT: one workgroup, a bitonic network in LDS */
+int sn_launch_order_sort(sn_order_ent *ents, int32_t n, void *stream);
+/* output row j = candidate j, every projection through select_emit */
+int sn_launch_order_gather(const sn_dev_select *sel,
+                           const sn_dev_batch *dev_batches,
+                           const sn_order_ent *cand,
+                           const int32_t *table_batch, void *stream);
+
 /* put-time patch materialization into a null-free fixed-width device body */
 int sn_launch_patch_apply(void *body, const int32_t *pos, const double *val,
                           int n, int kind, void *stream);

@@ -3136,3 +3136,454 @@ extern "C" int sn_launch_select_gather(const sn_dev_select *sel,
                      bitmap, counts, offsets, table_batch);
   return (int)hipGetLastError();
 }
+
+/* ================= ordered row scan =================
+ * SELECT cols WHERE preds ORDER BY key LIMIT k.  Pass 1 (k_select_mark) and
+ * k_tile_offsets have left the alive bitmap and the tile counts.  A radix
+ * select, 11 bits a pass from the top, finds the image T of the k-th smallest
+ * key among the alive rows; the rows below T and the first `need` rows equal
+ * to T (in scan order) are the result; one workgroup sorts them and the
+ * gather projects them in that order.  Nothing is read back in between. */
+
+/* the key of one row in two steps, so that a walk can issue the loads of
+ * several rows before it needs the first value.  order_load reads the value
+ * the way select_emit reads it: *vi the integer value, the f64 bit pattern or
+ * the STRING's global id, *fbits the f32 pattern; returns 0 for a NULL. */
+__device__ __forceinline__ int order_load(const sn_dev_order &od,
+                                          const sn_dev_col &c, int direct,
+                                          int row, long long *vi_,
+                                          unsigned *fbits_) {
+  int ok = 1, gid = 0, have = 0;
+  long long vi = 0;
+  unsigned fbits = 0;
+  if (direct) {
+    have = 1;
+    switch (c.kind) {
+      case SN_K_F64: vi = as_global((const long long *)c.body)[row]; break;
+      case SN_K_F64C8:
+        vi = as_global((const long long *)c.rle_vals)
+            [as_global((const uint8_t *)c.body)[row]];
+        break;
+      case SN_K_I64: vi = as_global((const long long *)c.body)[row]; break;
+      case SN_K_I32: vi = as_global((const int32_t *)c.body)[row]; break;
+      case SN_K_F32: fbits = as_global((const unsigned *)c.body)[row]; break;
+      case SN_K_I16: vi = as_global((const int16_t *)c.body)[row]; break;
+      case SN_K_S8: vi = as_global((const int8_t *)c.body)[row]; break;
+      case SN_K_U8: vi = as_global((const uint8_t *)c.body)[row] == 1; break;
+      default: have = 0; break;
+    }
+  }
+  if (!have) {
+    double vd = 0.0;
+    ok = read_general(c, row, &vd, &vi, &gid);
+    if (od.dtype == SN_TYPE_DOUBLE) vi = __double_as_longlong(vd);
+    else if (od.dtype == SN_TYPE_FLOAT) fbits = __float_as_uint((float)vd);
+    else if (od.dtype == SN_TYPE_STRING) vi = gid;
+  }
+  *vi_ = vi;
+  *fbits_ = fbits;
+  return ok;
+}
+
+/* key image from order_load's outputs: the class, and through *key the u64
+ * (0 for a NULL) */
+__device__ __forceinline__ int order_image(const sn_dev_order &od, int ok,
+                                           long long vi, unsigned fbits,
+                                           unsigned long long *key) {
+  if (!ok) { *key = 0; return od.null_cls; }
+  if (od.dtype == SN_TYPE_STRING)
+    vi = (unsigned)vi < (unsigned)od.nranks ? as_global(od.ranks)[(int)vi]
+                                            : 0x7fffffff;
+  *key = sn_order_image(od.dtype, vi, fbits, od.desc);
+  return SN_ORD_CLS_VALUE;
+}
+
+/* The walks below take one 1,024-row chunk at a time: cw points at its 16
+ * alive words, lane l of a wave owns bit l of word (tid + k * WG) >> 6.  All
+ * four words are loaded first, then all four keys, and only then does anything
+ * wait on a value: a block walks its tiles alone, so its pace is the number of
+ * dependent load latencies per chunk (two this way, eight when each word and
+ * each key is loaded where it is used). */
+#define ORDER_CHUNK_LOADS()                                                  \
+  uint64_t aw[CHUNK / WG];                                                   \
+  long long vi[CHUNK / WG];                                                  \
+  unsigned fb[CHUNK / WG];                                                   \
+  int ok[CHUNK / WG], live[CHUNK / WG];                                      \
+  _Pragma("unroll")                                                          \
+  for (int k = 0; k < CHUNK / WG; k++) aw[k] = cw[(tid + k * WG) >> 6];      \
+  _Pragma("unroll")                                                          \
+  for (int k = 0; k < CHUNK / WG; k++) {                                     \
+    const int row_ = base + tid + k * WG;                                    \
+    live[k] = (int)((aw[k] >> lane) & 1ull) && row_ < tile_end;              \
+    vi[k] = 0; fb[k] = 0; ok[k] = 0;                                         \
+    if (live[k]) ok[k] = order_load(od, c, direct, row_, &vi[k], &fb[k]);    \
+  }
+
+/* ---- radix select, counting half: the next digit of every alive row whose
+ * image still matches the prefix, into a per-block LDS histogram ---- */
+__global__ __launch_bounds__(WG, 4)
+void k_order_hist(sn_dev_order od, const sn_dev_batch *__restrict__ batches,
+                  const sn_dev_tile *__restrict__ tiles, int ntiles,
+                  const uint64_t *__restrict__ bitmap,
+                  const int32_t *__restrict__ counts,
+                  const sn_order_state *__restrict__ state,
+                  unsigned long long *__restrict__ hist, int pass, int shift) {
+  __shared__ unsigned shist[SN_ORD_HIST];
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned long long prefix = 0, himask = 0;
+  if (pass > 0) {
+    /* T is a NULL class: no digit is left to decide (uniform) */
+    if (state->cls != SN_ORD_CLS_VALUE) return;
+    prefix = state->prefix;
+    himask = ~0ull << (shift + SN_ORD_DIGIT_BITS);
+  }
+  for (int i = tid; i < SN_ORD_HIST; i += WG) shist[i] = 0;
+  __syncthreads();
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    if (counts[t] == 0) continue;                               /* uniform */
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, b.num_rows);
+    const int direct = b.clean;
+    const sn_dev_col &c = b.cols[od.cslot];
+    const uint64_t *tw = bitmap + (size_t)t * SN_SEL_TILE_WORDS;
+    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
+      const uint64_t *cw = tw + ((base - tile.row_start) / CHUNK) * (CHUNK / 64);
+      ORDER_CHUNK_LOADS();
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        if (aw[k] == 0) continue;                               /* uniform */
+        int bin = -1;
+        if (live[k]) {
+          unsigned long long key;
+          const int cls = order_image(od, ok[k], vi[k], fb[k], &key);
+          const int digit = 1 + (int)((key >> shift) & (SN_ORD_BINS - 1));
+          if (pass == 0)
+            bin = cls == SN_ORD_CLS_VALUE ? digit
+                : cls == SN_ORD_CLS_FIRST ? 0 : SN_ORD_BINS + 1;
+          else if (cls == SN_ORD_CLS_VALUE && ((key ^ prefix) & himask) == 0)
+            bin = digit;
+        }
+        /* the high digits of dates and prices put a whole wave in one bin:
+         * the lanes that agree with the first active lane add once */
+        const unsigned long long am = __ballot(bin >= 0);
+        if (am) {
+          const int leader = __ffsll((long long)am) - 1;
+          const int b0 = __shfl(bin, leader, 64);
+          const unsigned long long same = __ballot(bin == b0);
+          if (lane == leader) atomicAdd(&shist[b0], (unsigned)__popcll(same));
+          else if (bin >= 0 && bin != b0) atomicAdd(&shist[bin], 1u);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < SN_ORD_HIST; i += WG) {
+    const unsigned v = shist[i];
+    if (v) atomicAdd(&hist[i], (unsigned long long)v);
+  }
+}
+
+/* ---- radix select, deciding half: one workgroup finds the bin in which the
+ * running count reaches `need`, extends the prefix by its digit and leaves
+ * the rank wanted inside that bin ---- */
+__global__ __launch_bounds__(WG, 1)
+void k_order_pick(const unsigned long long *__restrict__ hist,
+                  sn_order_state *__restrict__ state, int pass, int shift,
+                  int k_eff) {
+  constexpr int PER = (SN_ORD_HIST + WG - 1) / WG;
+  __shared__ long long wsum[WG / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (pass > 0 && state->cls != SN_ORD_CLS_VALUE) return;       /* uniform */
+  const long long need = pass == 0 ? (long long)k_eff : state->need;
+  const unsigned long long prefix = pass == 0 ? 0 : state->prefix;
+  long long cnt[PER], mine = 0;
+#pragma unroll
+  for (int i = 0; i < PER; i++) {
+    const int bin = tid * PER + i;
+    cnt[i] = bin < SN_ORD_HIST ? (long long)hist[bin] : 0;
+    mine += cnt[i];
+  }
+  long long x = mine;                       /* inclusive scan within the wave */
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  if (lane == 63) wsum[wid] = x;
+  __syncthreads();                 /* also: every thread has read the state */
+  long long before = x - mine;
+  for (int w = 0; w < wid; w++) before += wsum[w];
+  /* the bin holding the row of 0-based rank need - 1: exactly one thread */
+  if (before < need && need <= before + mine) {
+    long long run = before;
+#pragma unroll
+    for (int i = 0; i < PER; i++) {
+      if (run < need && need <= run + cnt[i]) {
+        const int bin = tid * PER + i;
+        state->need = need - run;
+        if (pass == 0) {
+          state->cursor = 0;
+          state->cls = bin == 0 ? SN_ORD_CLS_FIRST
+                     : bin == SN_ORD_BINS + 1 ? SN_ORD_CLS_LAST
+                     : SN_ORD_CLS_VALUE;
+        }
+        if (bin >= 1 && bin <= SN_ORD_BINS)
+          state->prefix = prefix | ((unsigned long long)(bin - 1) << shift);
+        else
+          state->prefix = 0;
+      }
+      run += cnt[i];
+    }
+  }
+}
+
+/* rows of tile t equal to T, per tile */
+__global__ __launch_bounds__(WG, 4)
+void k_order_count(sn_dev_order od, const sn_dev_batch *__restrict__ batches,
+                   const sn_dev_tile *__restrict__ tiles, int ntiles,
+                   const uint64_t *__restrict__ bitmap,
+                   const int32_t *__restrict__ counts,
+                   const sn_order_state *__restrict__ state,
+                   int32_t *__restrict__ eq_counts) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int tcls = state->cls;
+  const unsigned long long tkey = state->prefix;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    if (counts[t] == 0) continue;                               /* uniform */
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, b.num_rows);
+    const int direct = b.clean;
+    const sn_dev_col &c = b.cols[od.cslot];
+    const uint64_t *tw = bitmap + (size_t)t * SN_SEL_TILE_WORDS;
+    int n = 0;                               /* this wave's equals (uniform) */
+    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
+      const uint64_t *cw = tw + ((base - tile.row_start) / CHUNK) * (CHUNK / 64);
+      ORDER_CHUNK_LOADS();
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        if (aw[k] == 0) continue;                               /* uniform */
+        int eq = 0;
+        if (live[k]) {
+          unsigned long long key;
+          const int cls = order_image(od, ok[k], vi[k], fb[k], &key);
+          eq = cls == tcls && key == tkey;
+        }
+        n += __popcll(__ballot(eq));
+      }
+    }
+    if (lane == 0 && n) (void)atomicAdd(&eq_counts[t], n);
+  }
+}
+
+/* ---- candidates: every alive row below T, and the rows equal to T whose
+ * scan-order rank among the equals is below `need` ---- */
+__global__ __launch_bounds__(WG, 4)
+void k_order_collect(sn_dev_order od, const sn_dev_batch *__restrict__ batches,
+                     const sn_dev_tile *__restrict__ tiles, int ntiles,
+                     const uint64_t *__restrict__ bitmap,
+                     const int32_t *__restrict__ counts,
+                     sn_order_state *__restrict__ state,
+                     const int64_t *__restrict__ eq_offsets,
+                     sn_order_ent *__restrict__ cand, int k_eff) {
+  __shared__ uint64_t seq[CHUNK / 64];       /* the chunk's equal rows */
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int tcls = state->cls;
+  const unsigned long long tkey = state->prefix;
+  const long long need = state->need;
+  const unsigned long long below_lane = (1ull << lane) - 1ull;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    if (counts[t] == 0) continue;                               /* uniform */
+    const sn_dev_tile tile = tiles[t];
+    const sn_dev_batch &b = batches[tile.batch];
+    const int tile_end = min(tile.row_start + SN_TILE_ROWS, b.num_rows);
+    const int direct = b.clean;
+    const sn_dev_col &c = b.cols[od.cslot];
+    const uint64_t *tw = bitmap + (size_t)t * SN_SEL_TILE_WORDS;
+    const unsigned long long pos_hi = (unsigned long long)tile.batch << 32;
+    long long eq_run = eq_offsets[t];        /* equals before this chunk */
+    for (int base = tile.row_start; base < tile_end; base += CHUNK) {
+      const uint64_t *cw = tw + ((base - tile.row_start) / CHUNK) * (CHUNK / 64);
+      unsigned long long key[CHUNK / WG], eqm[CHUNK / WG];
+      int rel[CHUNK / WG];                   /* 0 above T, 1 below, 2 equal */
+      int cl[CHUNK / WG];
+      ORDER_CHUNK_LOADS();
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        const int r = tid + k * WG;
+        key[k] = 0; rel[k] = 0; cl[k] = 0;
+        if (live[k]) {
+          cl[k] = order_image(od, ok[k], vi[k], fb[k], &key[k]);
+          if (cl[k] < tcls || (cl[k] == tcls && key[k] < tkey)) rel[k] = 1;
+          else if (cl[k] == tcls && key[k] == tkey) rel[k] = 2;
+        }
+        eqm[k] = __ballot(rel[k] == 2);
+        if (lane == 0) seq[r >> 6] = eqm[k];
+      }
+      __syncthreads();
+      long long chunk_eq = 0;
+#pragma unroll
+      for (int k = 0; k < CHUNK / WG; k++) {
+        const int r = tid + k * WG;
+        int take = rel[k] == 1;
+        if (rel[k] == 2) {
+          /* in-chunk rank by the word-popcount prefix, as k_select_gather */
+          long long rank = eq_run + __popcll(eqm[k] & below_lane);
+          for (int w = 0; w < (r >> 6); w++) rank += __popcll(seq[w]);
+          take = rank < need;
+        }
+        const unsigned long long tm = __ballot(take);
+        if (tm) {
+          const int leader = __ffsll((long long)tm) - 1;
+          int at = 0;
+          if (lane == leader) at = atomicAdd(&state->cursor, __popcll(tm));
+          at = __shfl(at, leader, 64);
+          const int o = at + __popcll(tm & below_lane);
+          if (take && o < k_eff) {           /* every store guarded by k_eff */
+            sn_order_ent ent;
+            ent.key = key[k];
+            ent.cp = ((unsigned long long)cl[k] << 62) | pos_hi |
+                     (unsigned long long)(unsigned)(base + r);
+            cand[o] = ent;
+          }
+        }
+      }
+#pragma unroll
+      for (int w = 0; w < CHUNK / 64; w++) chunk_eq += __popcll(seq[w]);
+      eq_run += chunk_eq;
+      __syncthreads();                       /* seq is rewritten next chunk */
+    }
+  }
+}
+
+extern "C" int sn_launch_order_select(const sn_dev_order *od,
+                                      const sn_dev_batch *dev_batches,
+                                      const sn_dev_tile *dev_tiles,
+                                      int32_t ntiles, const uint64_t *bitmap,
+                                      const int32_t *counts,
+                                      sn_order_state *state,
+                                      unsigned long long *hist,
+                                      int32_t *eq_counts, int64_t *eq_offsets,
+                                      int64_t *eq_total, sn_order_ent *cand,
+                                      int32_t k_eff, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ntiles <= 0 || k_eff < 1 || k_eff > SN_ORDER_MAX_LIMIT ||
+      od->npass < 1 || od->npass > SN_ORD_MAX_PASSES ||
+      od->cslot < 0 || od->cslot >= SN_DEV_MAX_COLS)
+    return (int)hipErrorInvalidValue;
+  const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
+  for (int p = 0; p < od->npass; p++) {
+    const int shift = SN_ORD_DIGIT_BITS * (od->npass - 1 - p);
+    unsigned long long *h = hist + (size_t)p * SN_ORD_HIST;
+    hipLaunchKernelGGL(k_order_hist, dim3(grid), dim3(WG), 0, s, *od,
+                       dev_batches, dev_tiles, ntiles, bitmap, counts, state,
+                       h, p, shift);
+    hipLaunchKernelGGL(k_order_pick, dim3(1), dim3(WG), 0, s, h, state, p,
+                       shift, k_eff);
+  }
+  hipLaunchKernelGGL(k_order_count, dim3(grid), dim3(WG), 0, s, *od,
+                     dev_batches, dev_tiles, ntiles, bitmap, counts, state,
+                     eq_counts);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+  int rc = sn_launch_tile_offsets(eq_counts, ntiles, eq_offsets, eq_total, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(k_order_collect, dim3(grid), dim3(WG), 0, s, *od,
+                     dev_batches, dev_tiles, ntiles, bitmap, counts, state,
+                     eq_offsets, cand, k_eff);
+  return (int)hipGetLastError();
+}
+
+/* ---- sort: one workgroup, a bitonic network over the next power of two of
+ * entries in LDS (16 B each: 128 KiB at 8,192), padded with entries above
+ * every real one ---- */
+#define ORDER_SORT_WG 1024
+__device__ __forceinline__ bool order_less(const sn_order_ent &a,
+                                           const sn_order_ent &b) {
+  const unsigned ca = (unsigned)(a.cp >> 62), cb = (unsigned)(b.cp >> 62);
+  if (ca != cb) return ca < cb;
+  if (a.key != b.key) return a.key < b.key;
+  return a.cp < b.cp;
+}
+
+__global__ __launch_bounds__(ORDER_SORT_WG, 1)
+void k_order_sort(sn_order_ent *__restrict__ ents, int n, int np2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  sn_order_ent *s = (sn_order_ent *)smem;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < np2; i += ORDER_SORT_WG) {
+    sn_order_ent e;
+    e.key = ~0ull; e.cp = ~0ull;
+    if (i < n) e = ents[i];
+    s[i] = e;
+  }
+  __syncthreads();
+  for (int k = 2; k <= np2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (np2 >> 1); t += ORDER_SORT_WG) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int l = i | j;
+        const bool up = (i & k) == 0;
+        const sn_order_ent a = s[i], b = s[l];
+        if (up ? order_less(b, a) : order_less(a, b)) { s[i] = b; s[l] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < n; i += ORDER_SORT_WG) ents[i] = s[i];
+}
+
+extern "C" int sn_launch_order_sort(sn_order_ent *ents, int32_t n,
+                                    void *stream) {
+  if (n < 0 || n > SN_ORDER_MAX_LIMIT || (n > 0 && !ents))
+    return (int)hipErrorInvalidValue;
+  if (n <= 1) return 0;
+  int np2 = 2;
+  while (np2 < n) np2 <<= 1;
+  hipLaunchKernelGGL(k_order_sort, dim3(1), dim3(ORDER_SORT_WG),
+                     (size_t)np2 * sizeof(sn_order_ent), (hipStream_t)stream,
+                     ents, n, np2);
+  return (int)hipGetLastError();
+}
+
+/* ---- ordered gather: output row j is candidate j.  The batch, and with it
+ * select_emit's switches, now differs from lane to lane: divergence on at
+ * most SN_ORDER_MAX_LIMIT rows ---- */
+__global__ __launch_bounds__(WG, 4)
+void k_order_gather(sn_dev_select sel,
+                    const sn_dev_batch *__restrict__ batches,
+                    const sn_order_ent *__restrict__ cand,
+                    const int32_t *__restrict__ table_batch) {
+  const long long j = (long long)blockIdx.x * WG + threadIdx.x;
+  if (j >= sel.out_rows) return;
+  const unsigned long long pos = cand[j].cp & SN_ORD_POS_MASK;
+  const int bi = (int)(pos >> 32), row = (int)(pos & 0xffffffffull);
+  const sn_dev_batch &b = batches[bi];
+  if (row >= b.num_rows) return;
+  for (int p = 0; p < sel.nproj; p++) {
+    const int otype = sel.otype[p];
+    if (otype == SN_SEL_ROWID) {
+      ((long long *)sel.val[p])[j] =
+          ((long long)table_batch[bi] << 32) | (long long)row;
+      sel.valid[p][j] = 1;
+      continue;
+    }
+    select_emit(b.cols[sel.cslot[p]], b.clean, otype, row, sel.val[p],
+                sel.valid[p], j);
+  }
+}
+
+extern "C" int sn_launch_order_gather(const sn_dev_select *sel,
+                                      const sn_dev_batch *dev_batches,
+                                      const sn_order_ent *cand,
+                                      const int32_t *table_batch,
+                                      void *stream) {
+  if (sel->nproj < 1 || sel->nproj > SN_SEL_MAX_PROJ || sel->out_rows <= 0 ||
+      sel->out_rows > SN_ORDER_MAX_LIMIT)
+    return (int)hipErrorInvalidValue;
+  const int grid = (int)((sel->out_rows + WG - 1) / WG);
+  hipLaunchKernelGGL(k_order_gather, dim3(grid), dim3(WG), 0,
+                     (hipStream_t)stream, *sel, dev_batches, cand, table_batch);
+  return (int)hipGetLastError();
+}

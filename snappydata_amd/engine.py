@@ -173,6 +173,15 @@ def lib():
         L.sn_scan_submit.argtypes = [C.c_void_p, C.POINTER(abi.SnPlan),
                                      C.c_int32, C.POINTER(C.c_int32),
                                      C.c_int64]
+        L.sn_scan_submit_ordered.restype = C.c_void_p
+        L.sn_scan_submit_ordered.argtypes = [C.c_void_p, C.POINTER(abi.SnPlan),
+                                             C.c_int32, C.POINTER(C.c_int32),
+                                             C.c_int32, C.c_int32, C.c_int64]
+        L.sn_order_key_h.restype = C.c_uint64
+        L.sn_order_key_h.argtypes = [C.c_int32, C.c_uint64, C.c_int32]
+        L.sn_order_dict_ranks.restype = C.c_int32
+        L.sn_order_dict_ranks.argtypes = [C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
         L.sn_rows_count.restype = C.c_int64
         L.sn_rows_count.argtypes = [C.c_void_p]
         L.sn_rows_fetch.restype = C.c_int32
@@ -451,7 +460,8 @@ class RowSet(Query):
 
     def kernel_ms_parts(self):
         """(mark, tile offsets, gather) device intervals in ms; kernel_ms()
-        is their sum."""
+        is their sum.  On an ordered select the third is the whole order
+        stage: radix select, tie quota, sort and ordered gather."""
         ms = (C.c_double * 3)()
         _check(lib().sn_rows_kernel_ms(self._h, ms), "rows_kernel_ms")
         return tuple(ms)
@@ -657,15 +667,31 @@ class Engine:
             raise EngineError(-1, last_error())
         return Query(self, h, plan)
 
-    def select(self, plan, cols, limit=0):
+    def select(self, plan, cols, limit=0, order_by=None, descending=False,
+               nulls_first=None):
         """SELECT cols WHERE plan's predicates [LIMIT limit] (limit <= 0:
         none): plan from abi.make_plan without aggregates or group columns,
         cols = table column ordinals or abi.PROJ_ROWID.  Rows come back in
         scan order (batch, then row ordinal).  Failures carry the engine's
-        status code."""
+        status code.
+
+        order_by = a table column ordinal: ORDER BY that column [DESC]
+        LIMIT limit, 1 <= limit <= abi.ORDER_MAX_LIMIT, selected and sorted on
+        the device; the key need not be among cols.  nulls_first None is
+        Spark's default (first ascending, last descending); rows with equal
+        keys keep their scan order."""
         cols = [int(c) for c in cols]
         arr = (C.c_int32 * max(len(cols), 1))(*cols)
-        h = lib().sn_scan_submit(self._h, C.byref(plan), len(cols), arr, limit)
+        if order_by is None:
+            h = lib().sn_scan_submit(self._h, C.byref(plan), len(cols), arr,
+                                     limit)
+        else:
+            flags = abi.ORDER_DESC if descending else 0
+            if nulls_first is not None:
+                flags |= abi.ORDER_NULLS_FIRST if nulls_first \
+                    else abi.ORDER_NULLS_LAST
+            h = lib().sn_scan_submit_ordered(self._h, C.byref(plan), len(cols),
+                                             arr, int(order_by), flags, limit)
         if not h:
             raise EngineError(lib().sn_last_error_code(), last_error())
         schema = self._schemas.get(plan.table, [])
