@@ -671,6 +671,9 @@ SNO_EXPORT int32_t sno_table_set_dim(sno_table *t, const int64_t *keys,
                                      int64_t n, const char *attr_payload,
                                      const int32_t *attr_lens) {
   if (!t || !keys || n <= 0) return SN_ERR_BADARG;
+  /* INT64_MIN marks an empty slot: not a legal key (the engine refuses it) */
+  for (int64_t i = 0; i < n; i++)
+    if (keys[i] == INT64_MIN) return SN_ERR_BADARG;
   int64_t cap = 2;
   while (cap < 2 * n + 1) cap <<= 1;
   t->dim_hk = (int64_t *)malloc((size_t)cap * 8);
@@ -703,7 +706,8 @@ SNO_EXPORT int32_t sno_table_set_dim(sno_table *t, const int64_t *keys,
 }
 
 static int dim_lookup(const sno_table *t, int64_t key) {
-  if (!t->dim_hk) return -1;
+  /* a fact key equal to the empty-slot mark must not match an empty slot */
+  if (!t->dim_hk || key == INT64_MIN) return -1;
   uint64_t h = sno_mix64((uint64_t)key) & (uint64_t)(t->dim_cap - 1);
   while (1) {
     int64_t k0 = t->dim_hk[h];

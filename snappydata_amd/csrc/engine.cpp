@@ -478,6 +478,12 @@ extern "C" int32_t sn_dim_put(sn_engine *e, int32_t dim, int64_t nkeys,
   std::lock_guard<std::mutex> gd(d->mu);
   if (d->from_table)
     return fail(SN_ERR_BADARG, "dimension was built from a column table");
+  /* INT64_MIN marks an empty slot of the device table: as a key it would be
+   * stored as "empty" and overwritten by a later insert (sn_dim_from_table
+   * refuses it likewise) */
+  for (int64_t i = 0; i < nkeys; i++)
+    if (keys[i] == INT64_MIN)
+      return fail(SN_ERR_BADARG, "INT64_MIN is not a legal dimension key");
   int64_t off = 0;
   for (int64_t i = 0; i < nkeys; i++) {
     d->keys.push_back(keys[i]);
@@ -741,26 +747,42 @@ extern "C" int32_t sn_dim_from_table(sn_engine *e, int32_t dim, int32_t table,
   } else {
     d->attr_dict.assign(1, std::string());
   }
-  /* dense LUT when the key span (from stats bounds) is small */
+  /* dense LUT when the key span (from stats bounds) is small.  The bounds
+   * must be ones the engine can trust: a batch whose key column carries
+   * update deltas or patches may hold keys outside its stats row (the rule
+   * of int_key_span), so it leaves the dimension on the hash table */
   bool have_span = !t->batches.empty();
   int64_t mn = INT64_MAX, mx = INT64_MIN;
   for (auto &b : t->batches) {
     if (!b.stats_valid || b.bounds_null.size() <= (size_t)key_col ||
-        b.bounds_null[key_col]) { have_span = false; break; }
+        b.bounds_null[key_col] || b.has_deltas ||
+        (b.had_patches.size() > (size_t)key_col && b.had_patches[key_col])) {
+      have_span = false;
+      break;
+    }
     mn = std::min(mn, b.lo_i[key_col]);
     mx = std::max(mx, b.hi_i[key_col]);
   }
-  if (have_span && mx >= mn && mx - mn + 1 <= (1ll << 24)) {
-    int64_t span = mx - mn + 1;
+  const int64_t span = have_span ? sn_lut_span(mn, mx) : 0;
+  if (span > 0) {
+    /* flags[2]: a build key outside [mn, mx] (zeroed with the build flags).
+     * The stats row of a put without deltas can still be wrong, so the
+     * kernel checks every key and a LUT that misses one is dropped. */
     int32_t *lut = (int32_t *)e->arena.alloc((size_t)span * 4);
+    int32_t oob = 1;
     if (lut &&
         hipMemsetAsync(lut, 0xff, (size_t)span * 4, e->stream) == hipSuccess &&
-        sn_launch_hash_to_lut(hk, hp, (long long)cap, lut, mn,
+        sn_launch_hash_to_lut(hk, hp, (long long)cap, lut, mn, mx, flags + 2,
                               e->stream) == 0 &&
-        hipStreamSynchronize(e->stream) == hipSuccess) {
+        hipStreamSynchronize(e->stream) == hipSuccess &&
+        hipMemcpy(&oob, flags + 2, 4, hipMemcpyDeviceToHost) == hipSuccess &&
+        oob == 0) {
       d->dev_lut = lut;
       d->lut_min = mn;
       d->lut_max = mx;
+    } else if (lut) {
+      (void)hipStreamSynchronize(e->stream);   /* nothing in flight on it */
+      e->arena.release(lut, (size_t)span * 4);
     }
   }
   return SN_OK;
@@ -795,8 +817,8 @@ static int dim_device_table(sn_engine *e, Dim *d) {
   if (!d->keys.empty()) {
     int64_t mn = d->keys[0], mx = d->keys[0];
     for (int64_t k : d->keys) { mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
-    int64_t span = mx - mn + 1;
-    if (span > 0 && span <= (1ll << 24)) {
+    const int64_t span = sn_lut_span(mn, mx);
+    if (span > 0) {
       std::vector<int32_t> lut((size_t)span, -1);
       for (size_t i = 0; i < d->keys.size(); i++)
         lut[(size_t)(d->keys[i] - mn)] = d->attr_gid[i];

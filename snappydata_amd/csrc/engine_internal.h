@@ -37,6 +37,18 @@ static inline int sn_type_width(sn_type_t dtype) {
   }
 }
 
+/* entries of a dense join LUT over the keys [mn, mx]: mx - mn + 1 when that
+ * lies in [1, SN_LUT_MAX_SPAN], else 0 (no LUT: the probe walks the hash
+ * table).  The difference is formed in uint64_t, where it is exact for every
+ * int64 pair with mx >= mn; in int64 it wraps for spans past 2^63 and a
+ * wrapped span can pass the bound. */
+#define SN_LUT_MAX_SPAN (1ll << 24)
+static inline int64_t sn_lut_span(int64_t mn, int64_t mx) {
+  if (mx < mn) return 0;
+  const uint64_t d = (uint64_t)mx - (uint64_t)mn;     /* span - 1 */
+  return d < (uint64_t)SN_LUT_MAX_SPAN ? (int64_t)d + 1 : 0;
+}
+
 #define SN_DEV_MAX_COLS 8      /* referenced columns per plan */
 
 /* column value kinds as seen by the kernel */
@@ -717,9 +729,12 @@ int sn_launch_join_build(const sn_dev_plan *plan, const sn_dev_plan *dev_plan,
                          const sn_dev_tile *dev_tiles, int32_t ntiles,
                          long long *hk, int32_t *hp, int cap_log2,
                          int has_attr, int32_t *flags, void *stream);
+/* lut covers [lmin, lmax]; a table key outside it is not written and sets
+ * oob[0] (one zeroed device word), so bounds the build keys do not honour
+ * cost the LUT, never memory */
 int sn_launch_hash_to_lut(const long long *hk, const int32_t *hp,
                           long long cap, int32_t *lut, long long lmin,
-                          void *stream);
+                          long long lmax, int32_t *oob, void *stream);
 
 /* wave-cooperative raw LZ4 block decode (f1 compressed-upload ingest);
  * err[0]: 0 ok, 1 malformed, 2 length mismatch */

@@ -254,9 +254,9 @@ def _run_case(eng, seed):
                 if s2 is not None:
                     group_cols.append(int(s2))
     elif r < 0.65 and num_cols:
+        # nullable columns included: a NULL key never joins
         jc = next((c for c in num_cols
-                   if schema[c][0] in (po.T_INT32, po.T_INT64) and
-                   not schema[c][1]), None)
+                   if schema[c][0] in (po.T_INT32, po.T_INT64)), None)
         if jc is not None:
             dk = np.unique(rng.integers(-5_000, 5_000, 3_000)).astype(np.int64)
             attrs = [b"G%d" % (int(x) % 6) for x in dk]
