@@ -144,6 +144,24 @@ def main():
     print(f"top {rs.count()} of {rs.rows_passed()} by v DESC:",
           list(zip(vals.tolist(), ordinals.tolist())))
 
+    # -- rows out of a join: SELECT o.key, o.v, s.nation FROM orders o
+    #    LEFT JOIN suppliers s ON o.key = s.key WHERE o.v >= 0.999
+    #    ORDER BY o.v DESC LIMIT 5; then the orders with NO supplier ---------
+    jplan = abi.make_plan(table=fact,
+                          preds=[dict(col=1, is_double=True, lo=0.999)],
+                          join=dict(dim=d2, fact_col=0))
+    rs = eng.select(jplan, [0, 1, abi.PROJ_DIM_ATTR], limit=5, order_by=1,
+                    descending=True, join_type=abi.RJOIN_LEFT_OUTER)
+    keys, _ = rs.column(0)
+    vals, _ = rs.column(1)
+    print(f"left outer join, top {rs.count()} of {rs.rows_passed()} by v:",
+          list(zip(keys.tolist(), [round(v, 5) for v in vals.tolist()],
+                   rs.strings(2))))
+    rs = eng.select(jplan, [0, abi.PROJ_ROWID],
+                    join_type=abi.RJOIN_LEFT_ANTI)
+    print(f"NOT EXISTS: {rs.count()} such orders have no supplier; all keys "
+          f"odd: {bool((rs.column(0)[0] % 2 == 1).all())}")
+
     eng.close()
 
 

@@ -616,6 +616,77 @@ sn_query *sn_scan_submit_ordered(sn_engine *e, const sn_plan *plan,
                                  int32_t order_col, int32_t order_flags,
                                  int64_t limit);
 
+/* ---- row scan over a dimension join: inner, left outer, left anti ----
+ * ColumnTableScan -> Filter -> HashJoinExec -> Project
+ * [-> TakeOrderedAndProject]: SELECT f.cols, d.attr FROM fact f JOIN dim d ON
+ * f.k = d.key WHERE preds [ORDER BY f.col] [LIMIT k], the probe running on
+ * the device between the filter and the projection (HashJoinExec.scala:285-520
+ * runs Inner, LeftOuter, LeftSemi and LeftAnti through one probe; so does
+ * this).  The dimension's keys are unique, so every type yields at most one
+ * output row per fact row.
+ *
+ *   sn_scan_submit_join
+ *       — plan, nproj, proj_cols, limit as in sn_scan_submit, with the join in
+ *         plan->join_dim / join_fact_col (join_mode SN_JOIN_SEMI).
+ *         sn_scan_submit and sn_scan_submit_ordered keep answering a join plan
+ *         with SN_ERR_UNSUPPORTED; this is the entry that takes one.
+ *         Join contract (a row JOINS iff its key is NOT NULL and equal to a
+ *         dimension key; INT64_MIN as a fact value never joins):
+ *           SN_RJOIN_INNER       rows that pass the predicates and join.  With
+ *                                no SN_PROJ_DIM_ATTR projected this is the
+ *                                left semi join.
+ *           SN_RJOIN_LEFT_OUTER  every row that passes the predicates; the
+ *                                attribute is NULL where the row does not join.
+ *           SN_RJOIN_LEFT_ANTI   rows that pass and do NOT join (Spark's
+ *                                LeftAnti, NOT EXISTS — not the null-aware
+ *                                NOT IN): NULL-key rows survive.
+ *         SN_PROJ_DIM_ATTR among proj_cols is the joined dimension row's
+ *         attribute: an int32 attribute id (sn_dim_attr_value gives its bytes)
+ *         plus the validity byte; an unjoined row (LEFT_OUTER only) has
+ *         validity 0 and value bytes 0.
+ *         order_col == SN_ORDER_NONE: sn_scan_submit's scan order and limit
+ *         rules (limit <= 0: none); order_flags must be 0.  Any other
+ *         order_col: sn_scan_submit_ordered's contract verbatim, limit bounds
+ *         included.  The key is a fact column: SN_PROJ_ROWID or
+ *         SN_PROJ_DIM_ATTR as order_col is SN_ERR_BADARG.
+ *         Checks run in this order: sn_scan_submit's (null arguments, unknown
+ *         table, naggs/ngroup non-zero SN_ERR_BADARG, npreds, nproj);
+ *         join_type outside 0..2, join_dim SN_JOIN_NONE or unknown, join_mode
+ *         not SN_JOIN_SEMI, an empty dimension, join_fact_col outside the
+ *         schema: SN_ERR_BADARG; a key column that is not INT32/INT64:
+ *         SN_ERR_UNSUPPORTED; the columns — a bad predicate or projection
+ *         ordinal, SN_PROJ_DIM_ATTR under LEFT_ANTI (there is no right side to
+ *         project) or on a dimension with sn_dim_num_attrs == 0:
+ *         SN_ERR_BADARG; a ninth distinct device column, the key column
+ *         counting: SN_ERR_UNSUPPORTED; the order checks; then SN_ERR_NOGPU.
+ *         The result is a rows handle: sn_rows_count, sn_rows_fetch,
+ *         sn_query_wait/_destroy/_kernel_ms and sn_query_result work as on
+ *         the other two, rows_passed counting the rows AFTER the join and
+ *         BEFORE the limit; the other calls return SN_ERR_UNSUPPORTED.
+ *         A sharded engine returns its local rows.
+ *   sn_dim_num_attrs
+ *       — distinct attribute values of dimension `dim` (the ids
+ *         SN_PROJ_DIM_ATTR yields are 0 .. that - 1); 0 for a dimension loaded
+ *         without attributes; SN_ERR_BADARG for a bad handle.
+ *   sn_dim_attr_value
+ *       — the bytes of attribute id `id`, in sn_table_dict_value's shape:
+ *         returns the length and, when buf is not NULL, copies the value
+ *         (cap < length is SN_ERR_BADARG; a NUL follows when there is room).
+ *         A bad dimension or id is SN_ERR_BADARG.  Needs no GPU. */
+#define SN_PROJ_DIM_ATTR   (-2)  /* pseudo-column: the joined dimension row's
+                                    attribute */
+#define SN_RJOIN_INNER      0
+#define SN_RJOIN_LEFT_OUTER 1
+#define SN_RJOIN_LEFT_ANTI  2
+#define SN_ORDER_NONE      (-1)  /* order_col: scan order, limit optional */
+sn_query *sn_scan_submit_join(sn_engine *e, const sn_plan *plan,
+                              int32_t join_type, int32_t nproj,
+                              const int32_t *proj_cols, int32_t order_col,
+                              int32_t order_flags, int64_t limit);
+int32_t   sn_dim_num_attrs(sn_engine *e, int32_t dim);
+int32_t   sn_dim_attr_value(sn_engine *e, int32_t dim, int32_t id, char *buf,
+                            int32_t cap);
+
 /* status code of the calling thread's last failure (pairs with
  * sn_last_error; lets callers of the pointer-returning submits tell
  * SN_ERR_UNSUPPORTED from SN_ERR_BADARG) */

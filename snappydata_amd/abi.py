@@ -25,6 +25,11 @@ SN_SEL_MAX_PROJ = 8
 # sn_scan_submit_ordered: order_flags bits and the largest limit
 ORDER_DESC, ORDER_NULLS_FIRST, ORDER_NULLS_LAST = 1, 2, 4
 ORDER_MAX_LIMIT = 8192
+# sn_scan_submit_join: the joined dimension row's attribute as a projection,
+# the join types, and "no ORDER BY" as its order_col
+PROJ_DIM_ATTR = -2
+RJOIN_INNER, RJOIN_LEFT_OUTER, RJOIN_LEFT_ANTI = 0, 1, 2
+ORDER_NONE = -1
 
 
 class SnBuf(C.Structure):

@@ -1817,6 +1817,9 @@ struct sn_query {
    * order stage, select to gather */
   bool ordered = false;
   int32_t ord_col = 0, ord_flags = 0;
+  /* join scan (sn_scan_submit_join): SN_RJOIN_*, -1 without a join.  INNER
+   * and LEFT_ANTI probe in pass 1; LEFT_OUTER only in pass 2's projection */
+  int32_t rjoin = -1;
   float sel_ms[3] = { 0.0f, 0.0f, 0.0f };  /* mark, offsets, gather */
   hipEvent_t sel_ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr,
                            nullptr };    /* (start, stop) of mark, offsets, gather */
@@ -2373,6 +2376,11 @@ static int32_t resolve_scan_set(sn_query *q, const sn_dev_plan &dp,
   /* a row-returning scan's set (projection-only columns behind the predicate
    * columns, no aggregate inputs, so no pac) is not an aggregate plan's */
   if (q->select) mix(0x73656c656374ull + (uint64_t)plan->npreds);
+  /* ... and a join scan's is not a plain select's: the fact key is a staged
+   * slot behind the predicate columns (INNER, LEFT_ANTI) or a projection-only
+   * one (LEFT_OUTER) */
+  if (q->rjoin >= 0)
+    mix(0x726a6f696eull + (q->rjoin == SN_RJOIN_LEFT_OUTER ? 1u : 0u));
 
   int64_t skip_count = 0;
   for (auto &b : t->batches)
@@ -3224,10 +3232,17 @@ static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
   if (hipMemsetAsync(counts, 0, (size_t)ntiles * 4, e->stream) != hipSuccess)
     return fail(SN_ERR_GENERIC, "tile count zero");
   if (q->sel_ev[0]) (void)hipEventRecord(q->sel_ev[0], e->stream);
-  rc = sn_launch_select_mark(&mp, (const sn_dev_plan *)mp_dev,
-                             (const sn_dev_batch *)set.db_dev,
-                             (const sn_dev_tile *)set.tl_dev, ntiles, bitmap,
-                             counts, e->stream);
+  if (q->rjoin == SN_RJOIN_INNER || q->rjoin == SN_RJOIN_LEFT_ANTI)
+    rc = sn_launch_select_mark_join(
+        &mp, (const sn_dev_plan *)mp_dev, (const sn_dev_batch *)set.db_dev,
+        (const sn_dev_tile *)set.tl_dev, ntiles,
+        q->rjoin == SN_RJOIN_INNER ? SN_MARK_INNER : SN_MARK_ANTI, bitmap,
+        counts, e->stream);
+  else
+    rc = sn_launch_select_mark(&mp, (const sn_dev_plan *)mp_dev,
+                               (const sn_dev_batch *)set.db_dev,
+                               (const sn_dev_tile *)set.tl_dev, ntiles, bitmap,
+                               counts, e->stream);
   if (q->sel_ev[1]) (void)hipEventRecord(q->sel_ev[1], e->stream);
   if (rc != 0)
     return fail(SN_ERR_GENERIC, "select mark launch: %s",
@@ -3254,10 +3269,22 @@ static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
   memset(&sel, 0, sizeof(sel));
   sel.nproj = q->sel_nproj;
   sel.out_rows = q->sel_rows;
+  if (q->rjoin >= 0) {
+    sel.jcslot = dp.jcslot;
+    sel.jis64 = (int32_t)((dp.i64_mask >> dp.jcslot) & 1u);
+    sel.jcap_log2 = dp.jcap_log2;
+    sel.jkeys = dp.jkeys;
+    sel.jpayload = dp.jpayload;
+    sel.jlut = dp.jlut;
+    sel.jlut_min = dp.jlut_min;
+    sel.jlut_max = dp.jlut_max;
+  }
   for (int p = 0; p < q->sel_nproj; p++) {
     const int32_t c = q->sel_cols[p];
-    sel.otype[p] = c == SN_PROJ_ROWID ? SN_SEL_ROWID : (int)t->schema[c].dtype;
-    sel.cslot[p] = c == SN_PROJ_ROWID ? 0 : q->cslot_of_col[c];
+    sel.otype[p] = c == SN_PROJ_ROWID ? SN_SEL_ROWID
+                   : c == SN_PROJ_DIM_ATTR ? SN_SEL_DIM_ATTR
+                                           : (int)t->schema[c].dtype;
+    sel.cslot[p] = c < 0 ? 0 : q->cslot_of_col[c];
     const size_t vb = (size_t)q->sel_rows * (size_t)q->sel_width[p];
     const size_t nb = (size_t)q->sel_rows;
     q->sel_val[p] = e->arena.alloc(vb);
@@ -3295,9 +3322,44 @@ static int32_t launch_select(sn_query *q, const sn_dev_plan &dp,
 /* ORDER BY request of sn_scan_submit_ordered */
 struct OrderReq { int32_t col, flags; };
 
+/* join request of sn_scan_submit_join: an SN_RJOIN_* type */
+struct JoinReq { int32_t type; };
+
+/* the join checks of sn_scan_submit_join, in the header's order; *out is the
+ * dimension.  Everything here runs without a device. */
+static int32_t check_scan_join(sn_engine *e, const Table *t,
+                               const sn_plan *plan, const JoinReq *jr,
+                               Dim **out) {
+  if (jr->type < SN_RJOIN_INNER || jr->type > SN_RJOIN_LEFT_ANTI)
+    return fail(SN_ERR_BADARG, "join type %d outside 0..2", jr->type);
+  if (plan->join_dim == SN_JOIN_NONE)
+    return fail(SN_ERR_BADARG, "sn_scan_submit_join needs plan->join_dim");
+  if (plan->join_dim < 0 || plan->join_dim >= (int32_t)e->dims.size())
+    return fail(SN_ERR_BADARG, "unknown dimension %d", plan->join_dim);
+  if (plan->join_mode != SN_JOIN_SEMI)
+    return fail(SN_ERR_BADARG,
+                "a row-returning join takes join_mode SN_JOIN_SEMI (the "
+                "attribute is a projection, SN_PROJ_DIM_ATTR)");
+  Dim *jd = e->dims[plan->join_dim].get();
+  {
+    std::lock_guard<std::mutex> gd(jd->mu);
+    if (jd->keys.empty() && !jd->dev_keys)
+      return fail(SN_ERR_BADARG, "empty dimension");
+  }
+  if (plan->join_fact_col < 0 ||
+      plan->join_fact_col >= (int32_t)t->schema.size())
+    return fail(SN_ERR_BADARG, "bad join key column %d", plan->join_fact_col);
+  const sn_type_t kt = t->schema[plan->join_fact_col].dtype;
+  if (kt != SN_TYPE_INT32 && kt != SN_TYPE_INT64)
+    return fail(SN_ERR_UNSUPPORTED, "join key must be int32/int64");
+  *out = jd;
+  return SN_OK;
+}
+
 static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
                                   int32_t nproj, const int32_t *proj_cols,
-                                  int64_t limit, const OrderReq *ord) {
+                                  int64_t limit, const OrderReq *ord,
+                                  const JoinReq *jr) {
   if (!e || !plan || !proj_cols) {
     fail(SN_ERR_BADARG, "null engine/plan/projection");
     return nullptr;
@@ -3309,8 +3371,10 @@ static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
          "a row-returning scan takes no aggregates and no group columns");
     return nullptr;
   }
-  if (plan->join_dim != SN_JOIN_NONE) {
-    fail(SN_ERR_UNSUPPORTED, "joins in row-returning scans are not supported");
+  if (!jr && plan->join_dim != SN_JOIN_NONE) {
+    fail(SN_ERR_UNSUPPORTED,
+         "sn_scan_submit and sn_scan_submit_ordered take no join "
+         "(sn_scan_submit_join does)");
     return nullptr;
   }
   if (plan->npreds < 0 || plan->npreds > SN_MAX_PREDS) {
@@ -3321,19 +3385,49 @@ static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
     fail(SN_ERR_BADARG, "nproj %d outside 1..%d", nproj, SN_SEL_MAX_PROJ);
     return nullptr;
   }
+  Dim *jd = nullptr;
+  if (jr && check_scan_join(e, t, plan, jr, &jd) != SN_OK) return nullptr;
   auto q = std::make_unique<sn_query>();
   q->e = e; q->t = t; q->plan = *plan;
   q->select = true;
   q->sel_nproj = nproj;
   q->sel_limit = limit > 0 ? limit : 0;
+  if (jr) q->rjoin = jr->type;
   /* predicate columns take the first device slots, projection-only ones
    * follow: pass 1 stages the former alone */
   if (collect_plan_columns(q.get()) != SN_OK) return nullptr;
-  const int npc = (int)q->used_cols.size();
+  int npc = (int)q->used_cols.size();
+  if (jr) {
+    /* INNER and LEFT_ANTI probe in pass 1: the key is staged with the
+     * predicate columns.  LEFT_OUTER's pass 1 is the plain one; the key is
+     * read by pass 2 alone, like a projected column. */
+    if (use_col(q.get(), plan->join_fact_col) < 0) {
+      fail(SN_ERR_UNSUPPORTED,
+           "predicates and join key name more than %d distinct columns",
+           SN_DEV_MAX_COLS);
+      return nullptr;
+    }
+    if (jr->type != SN_RJOIN_LEFT_OUTER) npc = (int)q->used_cols.size();
+  }
   for (int p = 0; p < nproj; p++) {
     const int32_t c = proj_cols[p];
     q->sel_cols[p] = c;
     if (c == SN_PROJ_ROWID) { q->sel_width[p] = 8; continue; }
+    if (jr && c == SN_PROJ_DIM_ATTR) {
+      if (jr->type == SN_RJOIN_LEFT_ANTI) {
+        fail(SN_ERR_BADARG,
+             "a left anti join has no right side to project (SN_PROJ_DIM_ATTR)");
+        return nullptr;
+      }
+      std::lock_guard<std::mutex> gd(jd->mu);
+      if (jd->attr_dict.empty()) {
+        fail(SN_ERR_BADARG, "dimension %d was loaded without attributes",
+             plan->join_dim);
+        return nullptr;
+      }
+      q->sel_width[p] = 4;
+      continue;
+    }
     if (c < 0 || c >= (int32_t)t->schema.size()) {
       fail(SN_ERR_BADARG, "bad projection column %d", c);
       return nullptr;
@@ -3346,6 +3440,15 @@ static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
     }
     const sn_type_t dt = t->schema[c].dtype;
     q->sel_width[p] = dt == SN_TYPE_STRING ? 4 : sn_type_width(dt);
+  }
+  if (ord && jr && ord->col == SN_ORDER_NONE) {
+    /* sn_scan_submit_join in scan order: sn_scan_submit's limit rules */
+    if (ord->flags != 0) {
+      fail(SN_ERR_BADARG, "order flags 0x%x without an order column",
+           (unsigned)ord->flags);
+      return nullptr;
+    }
+    ord = nullptr;
   }
   if (ord) {
     if (ord->col < 0 || ord->col >= (int32_t)t->schema.size()) {
@@ -3385,6 +3488,13 @@ static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
     return nullptr;
   }
   std::lock_guard<std::mutex> qg(e->query_mu);
+  if (jd) {
+    /* as on the aggregate route (resolve_join): the device table is built or
+     * reused under the dimension's mutex, inside the engine's one-submit
+     * section, before the table's mutex is taken (sn_dim_from_table's order) */
+    if (dim_device_table(e, jd) != SN_OK) return nullptr;
+    q->join_dim = jd;
+  }
   std::lock_guard<std::mutex> g(t->mu);
   sync_pending_stats(e, t);
   sn_dev_plan dp;
@@ -3405,7 +3515,7 @@ static sn_query *scan_submit_impl(sn_engine *e, const sn_plan *plan,
 extern "C" sn_query *sn_scan_submit(sn_engine *e, const sn_plan *plan,
                                     int32_t nproj, const int32_t *proj_cols,
                                     int64_t limit) {
-  return scan_submit_impl(e, plan, nproj, proj_cols, limit, nullptr);
+  return scan_submit_impl(e, plan, nproj, proj_cols, limit, nullptr, nullptr);
 }
 
 extern "C" sn_query *sn_scan_submit_ordered(sn_engine *e, const sn_plan *plan,
@@ -3415,7 +3525,44 @@ extern "C" sn_query *sn_scan_submit_ordered(sn_engine *e, const sn_plan *plan,
                                             int32_t order_flags,
                                             int64_t limit) {
   const OrderReq ord = { order_col, order_flags };
-  return scan_submit_impl(e, plan, nproj, proj_cols, limit, &ord);
+  return scan_submit_impl(e, plan, nproj, proj_cols, limit, &ord, nullptr);
+}
+
+extern "C" sn_query *sn_scan_submit_join(sn_engine *e, const sn_plan *plan,
+                                         int32_t join_type, int32_t nproj,
+                                         const int32_t *proj_cols,
+                                         int32_t order_col,
+                                         int32_t order_flags, int64_t limit) {
+  const JoinReq jr = { join_type };
+  const OrderReq ord = { order_col, order_flags };
+  return scan_submit_impl(e, plan, nproj, proj_cols, limit, &ord, &jr);
+}
+
+extern "C" int32_t sn_dim_num_attrs(sn_engine *e, int32_t dim) {
+  if (!e || dim < 0 || dim >= (int32_t)e->dims.size())
+    return fail(SN_ERR_BADARG, "bad dim handle");
+  Dim *d = e->dims[(size_t)dim].get();
+  std::lock_guard<std::mutex> gd(d->mu);
+  return (int32_t)d->attr_dict.size();
+}
+
+extern "C" int32_t sn_dim_attr_value(sn_engine *e, int32_t dim, int32_t id,
+                                     char *buf, int32_t cap) {
+  if (!e || dim < 0 || dim >= (int32_t)e->dims.size())
+    return fail(SN_ERR_BADARG, "bad dim handle");
+  Dim *d = e->dims[(size_t)dim].get();
+  std::lock_guard<std::mutex> gd(d->mu);
+  if (id < 0 || (size_t)id >= d->attr_dict.size())
+    return fail(SN_ERR_BADARG, "attribute id %d out of range", id);
+  const std::string &s = d->attr_dict[(size_t)id];
+  if (buf) {
+    if (cap < 0 || (size_t)cap < s.size())
+      return fail(SN_ERR_BADARG, "buffer of %d bytes for a %zu-byte value",
+                  cap, s.size());
+    memcpy(buf, s.data(), s.size());
+    if ((size_t)cap > s.size()) buf[s.size()] = 0;
+  }
+  return (int32_t)s.size();
 }
 
 static sn_query *rows_query(sn_query *q) {

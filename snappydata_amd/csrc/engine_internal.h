@@ -550,15 +550,34 @@ int sn_launch_dec_scan(const sn_dev_plan *plan, const sn_dev_plan *dev_plan,
 #define SN_SEL_MAX_PROJ 8
 #define SN_SEL_ROWID 8         /* otype of the ROWID pseudo-column (sn_type_t
                                   values are 0..7) */
+#define SN_SEL_DIM_ATTR 9      /* otype of the joined dimension row's attribute
+                                  (sn_scan_submit_join): int32 attribute id,
+                                  validity 0 where the row did not join */
 typedef struct {
   int32_t nproj, _p;
   int64_t out_rows;            /* min(matching rows, limit): every store is
                                   guarded by it */
   int32_t cslot[SN_SEL_MAX_PROJ];   /* device column slot (unused for ROWID) */
-  int32_t otype[SN_SEL_MAX_PROJ];   /* sn_type_t of the output, or ROWID */
+  int32_t otype[SN_SEL_MAX_PROJ];   /* sn_type_t of the output, ROWID or
+                                       DIM_ATTR */
   void *val[SN_SEL_MAX_PROJ];       /* dense typed output array */
   uint8_t *valid[SN_SEL_MAX_PROJ];  /* one validity byte per output row */
+  /* the dimension a DIM_ATTR projection probes (sn_dev_plan's j* fields; all
+   * zero without one): pass 2 reads the row's key again and looks it up,
+   * instead of pass 1 writing 4 B of payload for every scanned row */
+  int32_t jcslot;              /* device column slot of the fact key */
+  int32_t jis64;               /* the key column is INT64 */
+  int32_t jcap_log2, _pj;
+  const int64_t *jkeys;
+  const int32_t *jpayload;
+  const int32_t *jlut;
+  int64_t jlut_min, jlut_max;
 } sn_dev_select;
+
+/* pass 1's join step (k_select_mark): none, alive &= joined, alive &= ~joined */
+#define SN_MARK_NOJOIN 0
+#define SN_MARK_INNER  1
+#define SN_MARK_ANTI   2
 
 /* pass 1: plan->nused must be the number of PREDICATE column slots (they come
  * first in the descriptor set); counts[ntiles] zeroed by the caller */
@@ -566,6 +585,16 @@ int sn_launch_select_mark(const sn_dev_plan *plan, const sn_dev_plan *dev_plan,
                           const sn_dev_batch *dev_batches,
                           const sn_dev_tile *dev_tiles, int32_t ntiles,
                           uint64_t *bitmap, int32_t *counts, void *stream);
+/* pass 1 of a join scan (INNER, LEFT_ANTI): the fact key column is one of the
+ * staged slots (plan->jcslot < plan->nused) and plan->jkeys is set; after the
+ * predicates, the rows still alive are looked up and kept (SN_MARK_INNER) or
+ * dropped (SN_MARK_ANTI) when their key is NOT NULL and a dimension key */
+int sn_launch_select_mark_join(const sn_dev_plan *plan,
+                               const sn_dev_plan *dev_plan,
+                               const sn_dev_batch *dev_batches,
+                               const sn_dev_tile *dev_tiles, int32_t ntiles,
+                               int32_t mark, uint64_t *bitmap, int32_t *counts,
+                               void *stream);
 /* offsets[i] = counts[0] + ... + counts[i-1] in 64 bits, *total = the sum;
  * one workgroup, any n >= 0 */
 int sn_launch_tile_offsets(const int32_t *counts, int32_t n, int64_t *offsets,

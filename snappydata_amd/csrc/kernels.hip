@@ -793,6 +793,74 @@ __device__ __forceinline__ void probe_sweep(const sn_dev_plan *P, int clean,
   }
 }
 
+/* one key against the dimension, for the row scans (pass 1's probe_alive and
+ * pass 2's attribute projection share it): the payload, or a negative value
+ * when the key is absent.  Dense LUT when there is one, else the mix64
+ * linear-probe chain up to the LLONG_MIN empty mark.  LLONG_MIN itself never
+ * joins (it is no legal dimension key, and in the table it would "match" an
+ * empty slot).  The walk visits at most every slot once. */
+__device__ __forceinline__ int join_lookup(const GAS long long *jk,
+                                           const GAS int32_t *jp,
+                                           unsigned mask,
+                                           const GAS int32_t *lut,
+                                           long long lmin, long long lmax,
+                                           long long key) {
+  if (key == LLONG_MIN) return -1;
+  if (lut) return key >= lmin && key <= lmax ? lut[key - lmin] : -1;
+  unsigned h = (unsigned)mix64((unsigned long long)key) & mask;
+  for (unsigned it = 0; it <= mask; ++it) {
+    const long long k0 = jk[h];
+    if (k0 == key) return jp[h];
+    if (k0 == LLONG_MIN) break;
+    h = (h + 1) & mask;
+  }
+  return -1;
+}
+
+/* join step of a row scan's pass 1, after the predicates: only rows that are
+ * still alive are looked up (probe_sweep looks up every row of the chunk; at a
+ * few percent selectivity nearly all of those dependent loads are wasted), and
+ * a wave whose 64 rows are all dead skips its word.  joined = found & key
+ * validity; INNER keeps the joined rows, ANTI the others.  Lane 0 of the
+ * owning wave is the only reader and writer of an alive word, as everywhere. */
+template <int ANTI>
+__device__ __forceinline__ void probe_alive(const sn_dev_plan *P, int clean,
+                                            const double *sval,
+                                            const uint64_t *svalid,
+                                            uint64_t *salive) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const GAS long long *jk = (const GAS long long *)(uintptr_t)P->jkeys;
+  const GAS int32_t *jp = (const GAS int32_t *)(uintptr_t)P->jpayload;
+  const GAS int32_t *lut = (const GAS int32_t *)(uintptr_t)P->jlut;
+  const int cs = P->jcslot;
+  const unsigned mask = (1u << P->jcap_log2) - 1;
+  const int is_i64 = (P->i64_mask >> cs) & 1u;
+  const long long lmin = P->jlut_min, lmax = P->jlut_max;
+#pragma unroll
+  for (int k = 0; k < CHUNK / WG; k++) {
+    const int r = tid + k * WG, w = r >> 6;
+    unsigned lo = 0, hi = 0;
+    if (lane == 0) {
+      const uint64_t a = salive[w];
+      lo = (unsigned)a; hi = (unsigned)(a >> 32);
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    const uint64_t aw = ((uint64_t)hi << 32) | lo;
+    if (aw == 0) continue;                         /* wave-uniform */
+    int pay = -1;
+    if ((aw >> lane) & 1ull) {
+      const double xv = sval[(size_t)cs * CHUNK + r];
+      const long long key = is_i64 ? __double_as_longlong(xv) : (long long)xv;
+      pay = join_lookup(jk, jp, mask, lut, lmin, lmax, key);
+    }
+    uint64_t joined = __ballot(pay >= 0);
+    /* a NULL key never joins: its image slot holds a 0, which may be a key */
+    if (!clean) joined &= svalid[(size_t)cs * (CHUNK / 64) + w];
+    if (lane == 0) salive[w] = aw & (ANTI ? ~joined : joined);
+  }
+}
+
 /* ================= shared scan front end =================
  * Every scan kernel below is a row phase plugged into the same three pieces:
  * the LDS carve-up (scan_lds over engine_internal.h's sn_lds layout, which
@@ -2917,8 +2985,10 @@ extern "C" int sn_launch_dec_scan(const sn_dev_plan *plan,
  * alive rows into an LDS list and copies the projected columns out densely.
  * Row order is the scan order (tile, then row), so it is deterministic. */
 
-/* ---- pass 1: only the predicate columns (slots [0, plan.nused)) are staged ---- */
-template <int NC>
+/* ---- pass 1: only the predicate columns (slots [0, plan.nused)) are staged;
+ * a join scan (JOIN = SN_MARK_INNER / SN_MARK_ANTI) stages the fact key among
+ * them and ends its row phase with probe_alive ---- */
+template <int NC, int JOIN>
 __global__ __launch_bounds__(WG, 4)
 void k_select_mark(sn_dev_plan plan,
                    const sn_dev_plan *__restrict__ plan_g,
@@ -2938,6 +3008,9 @@ void k_select_mark(sn_dev_plan plan,
       if ((base & (SN_TILE_ROWS - 1)) == 0) t += (int)gridDim.x;
       alive_init(S.salive, S.sdead, rows, clean);
       pred_sweeps(S.P, npd, npi, clean, S.sval, S.svalid, S.salive);
+      if constexpr (JOIN != SN_MARK_NOJOIN)
+        probe_alive<JOIN == SN_MARK_ANTI>(S.P, clean, S.sval, S.svalid,
+                                          S.salive);
       /* each wave stores the words it owns (alive_init's ownership rule) */
       if ((tid & 63) == 0) {
         uint64_t *dst = bitmap + (size_t)t * SN_SEL_TILE_WORDS +
@@ -2967,11 +3040,42 @@ extern "C" int sn_launch_select_mark(const sn_dev_plan *plan,
   const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
   const size_t lds = (size_t)sn_lds_select(plan->nused).total;
   if (plan->nused <= 4)
-    hipLaunchKernelGGL((k_select_mark<4>), dim3(grid), dim3(WG), lds, s, *plan,
-                       dev_plan, dev_batches, dev_tiles, ntiles, bitmap, counts);
+    hipLaunchKernelGGL((k_select_mark<4, SN_MARK_NOJOIN>), dim3(grid), dim3(WG),
+                       lds, s, *plan, dev_plan, dev_batches, dev_tiles, ntiles,
+                       bitmap, counts);
   else
-    hipLaunchKernelGGL((k_select_mark<8>), dim3(grid), dim3(WG), lds, s, *plan,
-                       dev_plan, dev_batches, dev_tiles, ntiles, bitmap, counts);
+    hipLaunchKernelGGL((k_select_mark<8, SN_MARK_NOJOIN>), dim3(grid), dim3(WG),
+                       lds, s, *plan, dev_plan, dev_batches, dev_tiles, ntiles,
+                       bitmap, counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sn_launch_select_mark_join(const sn_dev_plan *plan,
+                                          const sn_dev_plan *dev_plan,
+                                          const sn_dev_batch *dev_batches,
+                                          const sn_dev_tile *dev_tiles,
+                                          int32_t ntiles, int32_t mark,
+                                          uint64_t *bitmap, int32_t *counts,
+                                          void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  /* the key is staged: without a table, or with the key slot outside the
+   * staged ones, the probe would read what pass 1 never wrote */
+  if (ntiles <= 0 || plan->nused < 1 || plan->nused > SN_DEV_MAX_COLS ||
+      (mark != SN_MARK_INNER && mark != SN_MARK_ANTI) || !plan->jkeys ||
+      !plan->jpayload || plan->jcslot < 0 || plan->jcslot >= plan->nused ||
+      plan->jcap_log2 < 1 || plan->jcap_log2 > 31)
+    return (int)hipErrorInvalidValue;
+  const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
+  const size_t lds = (size_t)sn_lds_select(plan->nused).total;
+#define KSM(NCv, Jv) hipLaunchKernelGGL((k_select_mark<NCv, Jv>), dim3(grid), \
+        dim3(WG), lds, s, *plan, dev_plan, dev_batches, dev_tiles, ntiles,    \
+        bitmap, counts)
+  if (mark == SN_MARK_INNER) {
+    if (plan->nused <= 4) KSM(4, SN_MARK_INNER); else KSM(8, SN_MARK_INNER);
+  } else {
+    if (plan->nused <= 4) KSM(4, SN_MARK_ANTI); else KSM(8, SN_MARK_ANTI);
+  }
+#undef KSM
   return (int)hipGetLastError();
 }
 
@@ -3068,6 +3172,44 @@ __device__ __forceinline__ void select_emit(const sn_dev_col &c, int direct,
   valid[o] = (uint8_t)ok;
 }
 
+/* the SN_SEL_DIM_ATTR projection of source row `row`: read the fact key the
+ * way select_emit reads a value (so it is the key pass 1 probed: patches,
+ * NULLs and run-length bodies included), look it up, store the attribute id.
+ * A row that does not join (NULL or absent key) gets id 0, validity 0. */
+__device__ __forceinline__ void select_emit_attr(const sn_dev_select &sel,
+                                                 const sn_dev_col &c,
+                                                 int direct, int row,
+                                                 void *val_, uint8_t *valid,
+                                                 long long o) {
+  int ok = 1, have = 0;
+  long long key = 0;
+  if (direct) {
+    have = 1;
+    switch (c.kind) {
+      case SN_K_I64: key = as_global((const long long *)c.body)[row]; break;
+      case SN_K_I32: key = as_global((const int32_t *)c.body)[row]; break;
+      default: have = 0; break;
+    }
+  }
+  if (!have) {
+    double vd = 0.0;
+    int gid = 0;
+    ok = read_general(c, row, &vd, &key, &gid);
+  }
+  int pay = -1;
+  if (ok)
+    pay = join_lookup((const GAS long long *)(uintptr_t)sel.jkeys,
+                      (const GAS int32_t *)(uintptr_t)sel.jpayload,
+                      (1u << sel.jcap_log2) - 1,
+                      (const GAS int32_t *)(uintptr_t)sel.jlut, sel.jlut_min,
+                      sel.jlut_max, key);
+  ((int32_t *)val_)[o] = pay >= 0 ? pay : 0;
+  valid[o] = (uint8_t)(pay >= 0);
+}
+
+/* ATTR = 0 is the gather of a scan without an attribute projection: the
+ * lookup is compiled out, so plain selects keep their registers and speed */
+template <int ATTR>
 __global__ __launch_bounds__(WG, 4)
 void k_select_gather(sn_dev_select sel,
                      const sn_dev_batch *__restrict__ batches,
@@ -3130,6 +3272,18 @@ void k_select_gather(sn_dev_select sel,
           }
           continue;
         }
+        if constexpr (ATTR) {
+          if (otype == SN_SEL_DIM_ATTR) {
+            const sn_dev_col &kc = b.cols[sel.jcslot];
+            for (int j = tid; j < nalive; j += WG) {
+              const long long o = running + j;
+              const int row = base + slist[j];
+              if (o >= sel.out_rows || row >= num_rows) break;
+              select_emit_attr(sel, kc, direct, row, val, valid, o);
+            }
+            continue;
+          }
+        }
         const sn_dev_col &c = b.cols[sel.cslot[p]];
         for (int j = tid; j < nalive; j += WG) {
           const long long o = running + j;
@@ -3144,6 +3298,22 @@ void k_select_gather(sn_dev_select sel,
   }
 }
 
+/* a DIM_ATTR projection needs the dimension descriptor (both gather launchers) */
+static bool sel_join_ok(const sn_dev_select *sel) {
+  for (int p = 0; p < sel->nproj; p++)
+    if (sel->otype[p] == SN_SEL_DIM_ATTR &&
+        (!sel->jkeys || !sel->jpayload || sel->jcslot < 0 ||
+         sel->jcslot >= SN_DEV_MAX_COLS || sel->jcap_log2 < 1 ||
+         sel->jcap_log2 > 31))
+      return false;
+  return true;
+}
+static bool sel_has_attr(const sn_dev_select *sel) {
+  for (int p = 0; p < sel->nproj; p++)
+    if (sel->otype[p] == SN_SEL_DIM_ATTR) return true;
+  return false;
+}
+
 extern "C" int sn_launch_select_gather(const sn_dev_select *sel,
                                        const sn_dev_batch *dev_batches,
                                        const sn_dev_tile *dev_tiles,
@@ -3153,12 +3323,17 @@ extern "C" int sn_launch_select_gather(const sn_dev_select *sel,
                                        const int32_t *table_batch,
                                        void *stream) {
   if (ntiles <= 0 || sel->nproj < 1 || sel->nproj > SN_SEL_MAX_PROJ ||
-      sel->out_rows <= 0)
+      sel->out_rows <= 0 || !sel_join_ok(sel))
     return (int)hipErrorInvalidValue;
   const int grid = sn_balanced_grid(ntiles, SN_GRID_CAP);
-  hipLaunchKernelGGL(k_select_gather, dim3(grid), dim3(WG), 0,
-                     (hipStream_t)stream, *sel, dev_batches, dev_tiles, ntiles,
-                     bitmap, counts, offsets, table_batch);
+  if (sel_has_attr(sel))
+    hipLaunchKernelGGL(k_select_gather<1>, dim3(grid), dim3(WG), 0,
+                       (hipStream_t)stream, *sel, dev_batches, dev_tiles,
+                       ntiles, bitmap, counts, offsets, table_batch);
+  else
+    hipLaunchKernelGGL(k_select_gather<0>, dim3(grid), dim3(WG), 0,
+                       (hipStream_t)stream, *sel, dev_batches, dev_tiles,
+                       ntiles, bitmap, counts, offsets, table_batch);
   return (int)hipGetLastError();
 }
 
@@ -3574,7 +3749,8 @@ extern "C" int sn_launch_order_sort(sn_order_ent *ents, int32_t n,
 
 /* ---- ordered gather: output row j is candidate j.  The batch, and with it
  * select_emit's switches, now differs from lane to lane: divergence on at
- * most SN_ORDER_MAX_LIMIT rows ---- */
+ * most SN_ORDER_MAX_LIMIT rows.  ATTR as in k_select_gather ---- */
+template <int ATTR>
 __global__ __launch_bounds__(WG, 4)
 void k_order_gather(sn_dev_select sel,
                     const sn_dev_batch *__restrict__ batches,
@@ -3594,6 +3770,13 @@ void k_order_gather(sn_dev_select sel,
       sel.valid[p][j] = 1;
       continue;
     }
+    if constexpr (ATTR) {
+      if (otype == SN_SEL_DIM_ATTR) {
+        select_emit_attr(sel, b.cols[sel.jcslot], b.clean, row, sel.val[p],
+                         sel.valid[p], j);
+        continue;
+      }
+    }
     select_emit(b.cols[sel.cslot[p]], b.clean, otype, row, sel.val[p],
                 sel.valid[p], j);
   }
@@ -3605,10 +3788,16 @@ extern "C" int sn_launch_order_gather(const sn_dev_select *sel,
                                       const int32_t *table_batch,
                                       void *stream) {
   if (sel->nproj < 1 || sel->nproj > SN_SEL_MAX_PROJ || sel->out_rows <= 0 ||
-      sel->out_rows > SN_ORDER_MAX_LIMIT)
+      sel->out_rows > SN_ORDER_MAX_LIMIT || !sel_join_ok(sel))
     return (int)hipErrorInvalidValue;
   const int grid = (int)((sel->out_rows + WG - 1) / WG);
-  hipLaunchKernelGGL(k_order_gather, dim3(grid), dim3(WG), 0,
-                     (hipStream_t)stream, *sel, dev_batches, cand, table_batch);
+  if (sel_has_attr(sel))
+    hipLaunchKernelGGL(k_order_gather<1>, dim3(grid), dim3(WG), 0,
+                       (hipStream_t)stream, *sel, dev_batches, cand,
+                       table_batch);
+  else
+    hipLaunchKernelGGL(k_order_gather<0>, dim3(grid), dim3(WG), 0,
+                       (hipStream_t)stream, *sel, dev_batches, cand,
+                       table_batch);
   return (int)hipGetLastError();
 }

@@ -177,6 +177,16 @@ def lib():
         L.sn_scan_submit_ordered.argtypes = [C.c_void_p, C.POINTER(abi.SnPlan),
                                              C.c_int32, C.POINTER(C.c_int32),
                                              C.c_int32, C.c_int32, C.c_int64]
+        L.sn_scan_submit_join.restype = C.c_void_p
+        L.sn_scan_submit_join.argtypes = [C.c_void_p, C.POINTER(abi.SnPlan),
+                                          C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_int32), C.c_int32,
+                                          C.c_int32, C.c_int64]
+        L.sn_dim_num_attrs.restype = C.c_int32
+        L.sn_dim_num_attrs.argtypes = [C.c_void_p, C.c_int32]
+        L.sn_dim_attr_value.restype = C.c_int32
+        L.sn_dim_attr_value.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_char_p, C.c_int32]
         L.sn_order_key_h.restype = C.c_uint64
         L.sn_order_key_h.argtypes = [C.c_int32, C.c_uint64, C.c_int32]
         L.sn_order_dict_ranks.restype = C.c_int32
@@ -448,11 +458,12 @@ class RowSet(Query):
     wait / kernel_ms / result (metrics only) / close work as on a Query; the
     aggregate-result calls raise EngineError(SN_ERR_UNSUPPORTED)."""
 
-    def __init__(self, eng, handle, plan, table, cols, dtypes):
+    def __init__(self, eng, handle, plan, table, cols, dtypes, dim=None):
         super().__init__(eng, handle, plan)
         self.table = table
         self.cols = list(cols)
         self._dtypes = list(dtypes)      # numpy dtype per projection
+        self.dim = dim                   # joined dimension (join selects)
 
     def count(self):
         """Rows returned (after the limit)."""
@@ -483,8 +494,14 @@ class RowSet(Query):
         return vals, valid.astype(bool)
 
     def strings(self, p):
-        """Projection p of a STRING column as a list of bytes (None = NULL)."""
-        if self.cols[p] == abi.PROJ_ROWID or \
+        """Projection p of a STRING column, or of abi.PROJ_DIM_ATTR (resolved
+        through the joined dimension), as a list of bytes (None = NULL)."""
+        if self.cols[p] == abi.PROJ_DIM_ATTR and self.dim is not None:
+            ids, valid = self.column(p)
+            look = {int(g): self._e.dim_attr_value(self.dim, int(g))
+                    for g in np.unique(ids[valid])}
+            return [look[int(g)] if ok else None for g, ok in zip(ids, valid)]
+        if self.cols[p] < 0 or \
                 self._e._schemas[self.table][self.cols[p]][0] != abi.T_STRING:
             raise EngineError(abi.ERR_BADARG, f"projection {p} is not a string")
         gids, valid = self.column(p)
@@ -668,7 +685,7 @@ class Engine:
         return Query(self, h, plan)
 
     def select(self, plan, cols, limit=0, order_by=None, descending=False,
-               nulls_first=None):
+               nulls_first=None, join_type=None):
         """SELECT cols WHERE plan's predicates [LIMIT limit] (limit <= 0:
         none): plan from abi.make_plan without aggregates or group columns,
         cols = table column ordinals or abi.PROJ_ROWID.  Rows come back in
@@ -679,25 +696,53 @@ class Engine:
         LIMIT limit, 1 <= limit <= abi.ORDER_MAX_LIMIT, selected and sorted on
         the device; the key need not be among cols.  nulls_first None is
         Spark's default (first ascending, last descending); rows with equal
-        keys keep their scan order."""
+        keys keep their scan order.
+
+        join_type = abi.RJOIN_INNER / RJOIN_LEFT_OUTER / RJOIN_LEFT_ANTI:
+        rows out of the join the plan names (abi.make_plan(..., join=dict(
+        dim=, fact_col=))); cols may then hold abi.PROJ_DIM_ATTR, the joined
+        dimension row's attribute (int32 ids; RowSet.strings resolves them,
+        None where a LEFT_OUTER row did not join).  None keeps the two plain
+        scans, which refuse a join plan."""
         cols = [int(c) for c in cols]
         arr = (C.c_int32 * max(len(cols), 1))(*cols)
-        if order_by is None:
+        flags = abi.ORDER_DESC if descending else 0
+        if nulls_first is not None:
+            flags |= abi.ORDER_NULLS_FIRST if nulls_first \
+                else abi.ORDER_NULLS_LAST
+        if join_type is not None:
+            h = lib().sn_scan_submit_join(
+                self._h, C.byref(plan), int(join_type), len(cols), arr,
+                abi.ORDER_NONE if order_by is None else int(order_by),
+                0 if order_by is None else flags, limit)
+        elif order_by is None:
             h = lib().sn_scan_submit(self._h, C.byref(plan), len(cols), arr,
                                      limit)
         else:
-            flags = abi.ORDER_DESC if descending else 0
-            if nulls_first is not None:
-                flags |= abi.ORDER_NULLS_FIRST if nulls_first \
-                    else abi.ORDER_NULLS_LAST
             h = lib().sn_scan_submit_ordered(self._h, C.byref(plan), len(cols),
                                              arr, int(order_by), flags, limit)
         if not h:
             raise EngineError(lib().sn_last_error_code(), last_error())
         schema = self._schemas.get(plan.table, [])
-        dtypes = [np.int64 if c == abi.PROJ_ROWID else _ROW_DTYPE[schema[c][0]]
-                  for c in cols]
-        return RowSet(self, h, plan, plan.table, cols, dtypes)
+        dtypes = [np.int64 if c == abi.PROJ_ROWID
+                  else np.int32 if c == abi.PROJ_DIM_ATTR
+                  else _ROW_DTYPE[schema[c][0]] for c in cols]
+        return RowSet(self, h, plan, plan.table, cols, dtypes,
+                      dim=plan.join_dim if join_type is not None else None)
+
+    def dim_num_attrs(self, dim):
+        """Distinct attribute values of a dimension (0: loaded without)."""
+        return _check(lib().sn_dim_num_attrs(self._h, dim), "dim_num_attrs")
+
+    def dim_attr_value(self, dim, aid):
+        """bytes of attribute id `aid` of dimension `dim` (the ids an
+        abi.PROJ_DIM_ATTR projection yields)."""
+        n = _check(lib().sn_dim_attr_value(self._h, dim, aid, None, 0),
+                   "dim_attr_value")
+        buf = C.create_string_buffer(n + 1)
+        _check(lib().sn_dim_attr_value(self._h, dim, aid, buf, n + 1),
+               "dim_attr_value")
+        return buf.raw[:n]
 
     def dict_value(self, table, col, gid):
         """bytes of global dictionary id `gid` of STRING column `col`."""
