@@ -37,7 +37,7 @@
  *         (core/.../aggregate/SnappyHashAggregateExec.scala:240-263,337-500)
  *         and driver-side CollectAggregateExec.executeCollect
  *         (core/.../aggregate/CollectAggregateExec.scala:46-91).
- *   sn_query_partials / sn_query_set_partials
+ *   sn_query_partials / sn_query_merge
  *       — the partial->final aggregation exchange the reference performs with a
  *         Spark ShuffleExchange between partial and final
  *         SnappyHashAggregateExec (requiredChildDistribution,
@@ -414,7 +414,17 @@ int32_t sn_query_partials_sharded2(sn_query *q, int32_t world, void *dst,
  * carry only its keys) with sn_query_merge. */
 int32_t sn_query_partials_sharded(sn_query *q, int32_t world, void *dst);
 /* merge n_blocks partial blocks (stride bytes apart, host memory) into the
- * final result; n_blocks=1 imports an already-all-reduced keyless block */
+ * final result; n_blocks=1 imports an already-all-reduced keyless block.
+ * The blocks come from other ranks, so each is checked against `stride`
+ * before any is folded, and nothing past `stride` bytes of a block is read.
+ * SN_ERR_BADARG, with the block's index and the reason in sn_last_error and
+ * the query's result left as it was, when
+ *   keyless: stride < (2 * naggs + 1) * 8;
+ *   grouped: stride < 8, n_slots < 0, 8 + n_slots * sizeof(slot) > stride,
+ *            or one of the group keys of a used slot has no NUL within its
+ *            SN_KEY_MAX bytes.
+ * Groups are matched on (key_null, key bytes) per column: a NULL key and a
+ * key whose text is "\x01" are two groups. */
 int32_t sn_query_merge(sn_query *q, const void *blocks, int64_t stride,
                        int32_t n_blocks);
 

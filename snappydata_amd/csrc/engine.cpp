@@ -53,6 +53,7 @@
 #include "../../include/snappy_engine.h"
 #include "engine_internal.h"
 #include "blob_format.h"
+#include "partial_format.h"
 
 /* ------------------------------------------------------------------ */
 /* error reporting                                                     */
@@ -1731,16 +1732,6 @@ extern "C" int64_t sn_table_get_blob(sn_engine *e, int32_t table, int32_t batch,
 /* ================================================================== */
 /* query plane                                                         */
 
-struct GroupOut {
-  std::string keys[SN_MAX_GROUPS];
-  bool key_null[SN_MAX_GROUPS] = { false, false };
-  double sums[SN_MAX_AGGS] = { 0 };
-  double counts[SN_MAX_AGGS] = { 0 };
-  double rowcount = 0;
-  int slot = 0;   /* dense accumulator slot (decimal queries look their
-                     exact values up by it after the key sort) */
-};
-
 /* decimal-query request threaded through the shared submit body */
 struct DecReq {
   int32_t naggs;
@@ -1770,7 +1761,6 @@ struct sn_query {
   bool gint[2] = { false, false };      /* integer group key (stats-ranged) */
   int64_t gmin[2] = { 0, 0 };           /* integer key minimum (slot base) */
   int gnull1 = -1, gnull2 = -1;         /* null slot index per group col (-1: none) */
-  bool grouped_nonnull_ok = true;
   /* grouped-mode device aggregate dedup: logical agg -> device sweep index
    * (-1 = COUNT(*), derived from the per-slot rowcount) */
   int agg_map[SN_MAX_AGGS];
@@ -1793,7 +1783,6 @@ struct sn_query {
   bool done = false;
   bool merged = false;
   std::vector<GroupOut> final_groups;
-  int status = SN_OK;
   /* exact DECIMAL query state (sn_query_submit_dec) */
   bool dec = false;
   int dec_ndev = 0;                      /* deduped device aggregates */
@@ -1834,18 +1823,6 @@ struct sn_query {
     }
   }
 };
-
-/* grouped partial-block slot layout (see include/snappy_engine.h) */
-struct PartialSlot {
-  char keys[SN_MAX_GROUPS][SN_KEY_MAX];
-  uint8_t key_null[SN_MAX_GROUPS];
-  uint8_t pad[6];
-  double sums[SN_MAX_AGGS];
-  double counts[SN_MAX_AGGS];
-  double rowcount;
-};
-static_assert(sizeof(PartialSlot) == SN_MAX_GROUPS * SN_KEY_MAX + 8 +
-              2 * SN_MAX_AGGS * 8 + 8, "partial slot layout");
 
 static bool batch_skippable(const Batch &b, const sn_plan *p, const Table *t) {
   if (!b.stats_valid || b.has_deltas || b.has_deletes) return false;
@@ -3916,13 +3893,33 @@ static void dec_finalize(sn_query *q, const unsigned long long *cells) {
   }
 }
 
+/* ================================================================== */
+/* read-back: everything below runs after the stream has synchronised  */
+
+/* The handle kinds an entry point does not serve.  Every caller checks its
+ * arguments first, then this, then sn_query_wait. */
+enum { REFUSE_ROWS = 1, REFUSE_DEC = 2 };
+static int32_t refuse_kind(const sn_query *q, const char *fn, int kinds) {
+  if ((kinds & REFUSE_ROWS) && q->select)
+    return fail(SN_ERR_UNSUPPORTED,
+                "%s is not supported on a row-returning query (its result is "
+                "rows, read with sn_rows_fetch)", fn);
+  if ((kinds & REFUSE_DEC) && q->dec)
+    return fail(SN_ERR_UNSUPPORTED,
+                "%s is not supported on an exact decimal query (its state is "
+                "128-bit fixed point, not the f64 partial layout)", fn);
+  return SN_OK;
+}
+#define REFUSE_KIND(q, kinds)                                   \
+  do {                                                          \
+    int32_t rk_ = refuse_kind((q), __func__, (kinds));          \
+    if (rk_ != SN_OK) return rk_;                               \
+  } while (0)
+
 extern "C" int32_t sn_query_result_dec(sn_query *q, int64_t row, int32_t agg,
                                        sn_dec_val *out) {
   if (!q || !out) return fail(SN_ERR_BADARG, "null query/out");
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_result_dec is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
+  REFUSE_KIND(q, REFUSE_ROWS);
   if (!q->dec) return fail(SN_ERR_BADARG, "not a decimal query");
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
@@ -3935,50 +3932,55 @@ extern "C" int32_t sn_query_result_dec(sn_query *q, int64_t row, int32_t agg,
   return SN_OK;
 }
 
+/* the rows stay on the device (sn_rows_fetch); the duration is the sum of
+ * the three kernels' own intervals, without the host readback gap */
+static int32_t wait_select(sn_query *q) {
+  float sum = 0.0f;
+  bool any = false;
+  for (int i = 0; i < 2 * q->sel_kernels; i += 2) {
+    float ms = 0.0f;
+    if (q->sel_ev[i] && q->sel_ev[i + 1] &&
+        hipEventElapsedTime(&ms, q->sel_ev[i], q->sel_ev[i + 1]) == hipSuccess) {
+      q->sel_ms[i / 2] = ms;
+      sum += ms;
+      any = true;
+    }
+  }
+  if (any) q->kernel_ms = sum;
+  return SN_OK;
+}
+
+static int32_t wait_decimal(sn_query *q) {
+  std::vector<unsigned long long> cells;
+  if (q->dec_out) {
+    cells.resize((size_t)q->nslots * sn_dec_row_cells(q->dec_ndev));
+    HIP_OR_FAIL(hipMemcpy(cells.data(), q->dec_out, cells.size() * 8,
+                          hipMemcpyDeviceToHost));
+  }
+  dec_finalize(q, q->dec_out ? cells.data() : nullptr);
+  return SN_OK;
+}
+
+static int32_t wait_f64(sn_query *q) {
+  size_t out_n = (size_t)q->nslots * q->out_stride;
+  q->host_out.resize(out_n);
+  if (out_n > 0 && q->dev_out)
+    HIP_OR_FAIL(hipMemcpy(q->host_out.data(), q->dev_out, out_n * 8,
+                          hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
 extern "C" int32_t sn_query_wait(sn_query *q) {
   if (!q) return SN_ERR_BADARG;
-  if (!q->done && q->select) {
-    /* the rows stay on the device (sn_rows_fetch); the duration is the sum
-     * of the three kernels' own intervals, without the host readback gap */
-    HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
-    float sum = 0.0f;
-    bool any = false;
-    for (int i = 0; i < 2 * q->sel_kernels; i += 2) {
-      float ms = 0.0f;
-      if (q->sel_ev[i] && q->sel_ev[i + 1] &&
-          hipEventElapsedTime(&ms, q->sel_ev[i], q->sel_ev[i + 1]) == hipSuccess) {
-        q->sel_ms[i / 2] = ms;
-        sum += ms;
-        any = true;
-      }
-    }
-    if (any) q->kernel_ms = sum;
-    q->done = true;
-  }
-  if (!q->done && q->dec) {
-    HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
-    std::vector<unsigned long long> cells;
-    if (q->dec_out) {
-      cells.resize((size_t)q->nslots * sn_dec_row_cells(q->dec_ndev));
-      HIP_OR_FAIL(hipMemcpy(cells.data(), q->dec_out, cells.size() * 8,
-                            hipMemcpyDeviceToHost));
-    }
-    dec_finalize(q, q->dec_out ? cells.data() : nullptr);
-    if (q->ev_start && q->ev_stop)
-      (void)hipEventElapsedTime(&q->kernel_ms, q->ev_start, q->ev_stop);
-    q->done = true;
-  }
-  if (!q->done) {
-    HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
-    size_t out_n = (size_t)q->nslots * q->out_stride;
-    q->host_out.resize(out_n);
-    if (out_n > 0 && q->dev_out)
-      HIP_OR_FAIL(hipMemcpy(q->host_out.data(), q->dev_out, out_n * 8,
-                            hipMemcpyDeviceToHost));
-    if (q->ev_start && q->ev_stop)
-      (void)hipEventElapsedTime(&q->kernel_ms, q->ev_start, q->ev_stop);
-    q->done = true;
-  }
+  if (q->done) return SN_OK;
+  HIP_OR_FAIL(hipStreamSynchronize(q->e->stream));
+  int32_t rc = q->select ? wait_select(q)
+               : q->dec  ? wait_decimal(q) : wait_f64(q);
+  if (rc != SN_OK) return rc;
+  /* an aggregate scan is bracketed by one event pair; a row scan has none */
+  if (q->ev_start && q->ev_stop)
+    (void)hipEventElapsedTime(&q->kernel_ms, q->ev_start, q->ev_stop);
+  q->done = true;
   return SN_OK;
 }
 
@@ -4007,139 +4009,128 @@ extern "C" int32_t sn_engine_jit_count(sn_engine *e) {
   return e ? sn_jit_cache_count(e->jit) : 0;
 }
 
-/* local accumulators -> GroupOut list (pre-merge view) */
-static void local_groups(sn_query *q, std::vector<GroupOut> *out) {
+/* group-key columns of the result: a dimension-attribute group leads them */
+static int eff_ngroup(const sn_query *q) {
+  return q->join_group ? 1 + q->plan.ngroup : q->plan.ngroup;
+}
+
+/* how this query's accumulator rows read (partial_format.h) */
+static AccRowLayout row_layout(const sn_query *q) {
   const sn_plan &p = q->plan;
-  Table *t = q->t;
-  if (q->sparse) {
-    /* hash-aggregate results: compacted (key, accumulator-row) pairs.
-     * Keys surface as decimal text like the dense integer-key path (the
-     * partial-block and result formats stay shared). */
-    const int naggs1 = (q->pac ? 2 : 1) * q->dev_naggs + 1;
-    const bool packed = p.ngroup == 2;
-    auto fill = [&](const double *row) -> GroupOut {
-      GroupOut g;
-      g.rowcount = row[naggs1 - 1];
-      for (int a = 0; a < p.naggs; a++) {
-        int di = q->agg_map[a];
-        double s = di < 0 ? g.rowcount : row[di];
-        int k = p.aggs[a].kind;
-        if (di >= 0 && (k == SN_AGG_MIN || k == SN_AGG_MAX)) {
-          /* sparse rows bypass k_reduce: decode the ord-u64 cell here */
-          unsigned long long o;
-          memcpy(&o, &row[di], 8);
-          s = sn_ord_f64_h(o);
-        }
-        g.sums[a] = s;
-        g.counts[a] = (di < 0 || !q->pac) ? g.rowcount
-                                          : row[q->dev_naggs + di];
-      }
-      return g;
-    };
-    for (size_t i = 0; i < q->sparse_n; i++) {
-      const double *row = &q->sparse_rows[i * naggs1];
-      if (row[naggs1 - 1] == 0.0) continue;
-      GroupOut g = fill(row);
-      long long key = q->sparse_keys[i];
-      if (packed) {
-        g.keys[0] = std::to_string((int32_t)((unsigned long long)key >> 32));
-        g.keys[1] = std::to_string((int32_t)(unsigned)key);
-      } else {
-        g.keys[0] = std::to_string(key);
-      }
-      out->push_back(std::move(g));
-    }
-    if (!q->sparse_null_row.empty() &&
-        q->sparse_null_row[naggs1 - 1] > 0.0) {
-      GroupOut g = fill(q->sparse_null_row.data());
-      g.key_null[0] = true;               /* the NULL-key group */
-      out->push_back(std::move(g));
-    }
-    return;
+  AccRowLayout L;
+  L.form = q->sparse ? SN_ROW_SPARSE
+           : eff_ngroup(q) == 0 ? SN_ROW_KEYLESS : SN_ROW_DENSE;
+  L.naggs = p.naggs; L.na_t = q->na_t; L.dev_naggs = q->dev_naggs;
+  L.pac = q->pac;
+  for (int a = 0; a < SN_MAX_AGGS; a++) {
+    L.agg_map[a] = q->agg_map[a];
+    L.kinds[a] = p.aggs[a].kind;
   }
-  /* concurrent ingest may be interning new dictionary entries; group ids
-   * recorded at submit stay valid (dictionaries only grow) but the vector
-   * needs the lock for stability */
-  std::lock_guard<std::mutex> g(t->mu);
-  for (int s = 0; s < q->nslots; s++) {
-    const double *row = &q->host_out[(size_t)s * q->out_stride];
-    double rowcount = row[2 * q->na_t];
-    if ((p.ngroup > 0 || q->join_group) && rowcount == 0.0) continue;
+  L.rowcount_at = acc_rowcount_at(L.form, L.na_t, L.dev_naggs, L.pac);
+  return L;
+}
+
+/* hash-aggregate results: compacted (key, accumulator-row) pairs.  Keys
+ * surface as decimal text like the dense integer-key path (the partial-block
+ * and result formats stay shared). */
+static void sparse_groups(sn_query *q, const AccRowLayout &L,
+                          std::vector<GroupOut> *out) {
+  const size_t width = (size_t)L.rowcount_at + 1;
+  const bool packed = q->plan.ngroup == 2;
+  for (size_t i = 0; i < q->sparse_n; i++) {
+    const double *row = &q->sparse_rows[i * width];
+    if (!acc_row_occupied(L, row)) continue;
     GroupOut g;
-    g.rowcount = rowcount;
-    g.slot = s;
-    for (int a = 0; a < p.naggs; a++) {
-      if (p.ngroup == 0 && !q->join_group) {
-        /* keyless MIN/MAX plans run the grouped (pac) layout with 1 slot:
-         * counts land at [naggs + a] instead of the keyless [na_t + a] */
-        g.sums[a] = row[a];
-        g.counts[a] = q->pac ? row[p.naggs + a] : row[q->na_t + a];
-      } else {
-        /* grouped: deduped device sweeps; COUNT(*) = rowcount; per-agg
-         * counts live at [dev_naggs + di] when the pac layout ran
-         * (nullable aggregate inputs), else counts == rowcount */
-        int di = q->agg_map[a];
-        g.sums[a] = di < 0 ? rowcount : row[di];
-        g.counts[a] = (di < 0 || !q->pac) ? rowcount
-                                          : row[q->dev_naggs + di];
-      }
-    }
-    if (q->join_group) {
-      std::lock_guard<std::mutex> gd(q->join_dim->mu);
-      if (p.ngroup >= 1) {
-        /* composite: attr-major, fact minor */
-        g.keys[0] = q->join_dim->attr_dict[s / q->fact_slots];
-        const int f = s % q->fact_slots;
-        int c0 = p.group_cols[0];
-        if (q->gint[0]) g.keys[1] = std::to_string(q->gmin[0] + f);
-        else if (f == q->gnull1) g.key_null[1] = true;
-        else g.keys[1] = t->gdict[c0][f];
-      } else {
-        g.keys[0] = q->join_dim->attr_dict[s];
-      }
-    } else if (p.ngroup >= 1) {
-      int c0 = p.group_cols[0];
-      int g1 = s / q->g2cap;
-      if (q->gint[0]) g.keys[0] = std::to_string(q->gmin[0] + g1);
-      else if (g1 == q->gnull1) g.key_null[0] = true;
-      else g.keys[0] = t->gdict[c0][g1];
-      if (p.ngroup == 2) {
-        int c1 = p.group_cols[1];
-        int g2 = s % q->g2cap;
-        if (q->gint[1]) g.keys[1] = std::to_string(q->gmin[1] + g2);
-        else if (g2 == q->gnull2) g.key_null[1] = true;
-        else g.keys[1] = t->gdict[c1][g2];
-      }
+    acc_row_decode(L, row, &g);
+    long long key = q->sparse_keys[i];
+    if (packed) {
+      g.keys[0] = std::to_string((int32_t)((unsigned long long)key >> 32));
+      g.keys[1] = std::to_string((int32_t)(unsigned)key);
+    } else {
+      g.keys[0] = std::to_string(key);
     }
     out->push_back(std::move(g));
   }
-  if (p.ngroup == 0 && !q->join_group && out->empty()) out->push_back(GroupOut());
+  if (!q->sparse_null_row.empty() &&
+      acc_row_occupied(L, q->sparse_null_row.data())) {
+    GroupOut g;
+    acc_row_decode(L, q->sparse_null_row.data(), &g);
+    g.key_null[0] = true;               /* the NULL-key group */
+    out->push_back(std::move(g));
+  }
 }
 
-static void finalize_groups(sn_query *q, std::vector<GroupOut> &groups) {
-  std::sort(groups.begin(), groups.end(), [](const GroupOut &a, const GroupOut &b) {
-    for (int i = 0; i < SN_MAX_GROUPS; i++) {
-      if (a.key_null[i] != b.key_null[i]) return !a.key_null[i];
-      int c = a.keys[i].compare(b.keys[i]);
-      if (c) return c < 0;
+/* key `at` of g from index i of the dense slot space of group column gc: an
+ * integer key counts up from its minimum, the null slot is NULL, anything
+ * else is a dictionary entry.  The caller holds t->mu. */
+static void dense_key(const sn_query *q, int gc, int i, GroupOut *g, int at) {
+  if (q->gint[gc]) g->keys[at] = std::to_string(q->gmin[gc] + i);
+  else if (i == (gc == 0 ? q->gnull1 : q->gnull2)) g->key_null[at] = true;
+  else g->keys[at] = q->t->gdict[q->plan.group_cols[gc]][i];
+}
+
+static void dense_groups(sn_query *q, const AccRowLayout &L,
+                         std::vector<GroupOut> *out) {
+  const sn_plan &p = q->plan;
+  const bool keyless = L.form == SN_ROW_KEYLESS;
+  /* concurrent ingest may be interning new dictionary entries; group ids
+   * recorded at submit stay valid (dictionaries only grow) but the vector
+   * needs the lock for stability */
+  std::lock_guard<std::mutex> gt(q->t->mu);
+  std::unique_lock<std::mutex> gd;
+  if (q->join_group) gd = std::unique_lock<std::mutex>(q->join_dim->mu);
+  for (int s = 0; s < q->nslots; s++) {
+    const double *row = &q->host_out[(size_t)s * q->out_stride];
+    if (!keyless && !acc_row_occupied(L, row)) continue;
+    GroupOut g;
+    g.slot = s;
+    acc_row_decode(L, row, &g);
+    if (q->join_group && p.ngroup >= 1) {
+      /* composite: attr-major, fact minor */
+      g.keys[0] = q->join_dim->attr_dict[s / q->fact_slots];
+      dense_key(q, 0, s % q->fact_slots, &g, 1);
+    } else if (q->join_group) {
+      g.keys[0] = q->join_dim->attr_dict[s];
+    } else if (p.ngroup >= 1) {
+      dense_key(q, 0, s / q->g2cap, &g, 0);
+      if (p.ngroup == 2) dense_key(q, 1, s % q->g2cap, &g, 1);
     }
-    return false;
-  });
-  q->final_groups = groups;
+    out->push_back(std::move(g));
+  }
+  if (keyless && out->empty()) out->push_back(GroupOut());
+}
+
+/* local accumulators -> GroupOut list (pre-merge view) */
+static void local_groups(sn_query *q, std::vector<GroupOut> *out) {
+  const AccRowLayout L = row_layout(q);
+  if (q->sparse) sparse_groups(q, L, out);
+  else dense_groups(q, L, out);
+}
+
+static void finalize_groups(sn_query *q, std::vector<GroupOut> &&groups) {
+  std::sort(groups.begin(), groups.end(), GroupKeyLess());
+  q->final_groups = std::move(groups);
+}
+
+/* the result rows, unless a merge or an earlier call already left them */
+static bool final_groups_ready(const sn_query *q) {
+  return !q->final_groups.empty() || q->merged;
+}
+static void ensure_final_groups(sn_query *q) {
+  if (final_groups_ready(q)) return;
+  std::vector<GroupOut> groups;
+  local_groups(q, &groups);
+  finalize_groups(q, std::move(groups));
 }
 
 static int32_t result_fill_page(sn_query *q, int64_t offset, sn_result *out) {
   if (!q || !out || offset < 0) return SN_ERR_BADARG;
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
-  if (q->final_groups.empty() && !q->merged) {
-    std::vector<GroupOut> groups;
-    local_groups(q, &groups);
-    finalize_groups(q, groups);
-  }
+  ensure_final_groups(q);
   memset(out, 0, sizeof(*out));
   const sn_plan &p = q->plan;
-  out->ngroup = q->join_group ? 1 + p.ngroup : p.ngroup;
+  out->ngroup = eff_ngroup(q);
   out->naggs = p.naggs;
   int64_t total = (int64_t)q->final_groups.size();
   int64_t start = offset < total ? offset : total;
@@ -4150,21 +4141,12 @@ static int32_t result_fill_page(sn_query *q, int64_t offset, sn_result *out) {
   for (int32_t i = 0; i < out->nrows; i++) {
     GroupOut &g = q->final_groups[(size_t)(start + i)];
     for (int k = 0; k < out->ngroup; k++) {
-      strncpy(out->keys[i][k], g.keys[k].c_str(), SN_KEY_MAX - 1);
+      group_key_put(out->keys[i][k], g.keys[k]);
       out->key_is_null[i][k] = g.key_null[k] ? 1 : 0;
     }
-    for (int a = 0; a < p.naggs; a++) {
-      const sn_agg &ag = p.aggs[a];
-      if (ag.kind == SN_AGG_COUNT_STAR) {
-        out->vals[i][a] = g.sums[a];
-      } else if (ag.kind == SN_AGG_AVG) {
-        if (g.counts[a] > 0) out->vals[i][a] = g.sums[a] / g.counts[a];
-        else out->val_is_null[i][a] = 1;
-      } else {
-        if (g.counts[a] > 0) out->vals[i][a] = g.sums[a];
-        else out->val_is_null[i][a] = 1;
-      }
-    }
+    for (int a = 0; a < p.naggs; a++)
+      if (!group_value(g, a, p.aggs[a].kind, &out->vals[i][a]))
+        out->val_is_null[i][a] = 1;
     out->rows_passed += (int64_t)g.rowcount;
   }
   return SN_OK;
@@ -4190,10 +4172,8 @@ extern "C" int32_t sn_query_result(sn_query *q, sn_result *out) {
  * global-atomic grouped path): fills up to one page from `offset`. */
 extern "C" int32_t sn_query_result_page(sn_query *q, int64_t offset,
                                         sn_result *out) {
-  if (q && q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_result_page is not supported on a row-returning query "
-                "(its result is rows, read with sn_rows_fetch)");
+  if (!q) return SN_ERR_BADARG;
+  REFUSE_KIND(q, REFUSE_ROWS);
   return result_fill_page(q, offset, out);
 }
 
@@ -4204,49 +4184,18 @@ extern "C" int32_t sn_query_result_page(sn_query *q, int64_t offset,
 extern "C" int32_t sn_query_order_by(sn_query *q, int32_t agg_idx,
                                      int32_t descending, int64_t k) {
   if (!q) return SN_ERR_BADARG;
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_order_by is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
-  if (q->dec)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_order_by is not supported on an exact decimal query (its "
-                "state is 128-bit fixed point, not the f64 partial layout)");
+  REFUSE_KIND(q, REFUSE_ROWS | REFUSE_DEC);
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
-  if (q->final_groups.empty() && !q->merged) {
-    std::vector<GroupOut> groups;
-    local_groups(q, &groups);
-    finalize_groups(q, groups);
-  }
+  ensure_final_groups(q);
   const sn_plan &p = q->plan;
   if (agg_idx >= p.naggs) return fail(SN_ERR_BADARG, "agg_idx out of range");
-  if (agg_idx >= 0) {
-    const sn_agg &ag = p.aggs[agg_idx];
-    auto val_of = [&](const GroupOut &g, double *v) -> bool {
-      if (ag.kind == SN_AGG_COUNT_STAR) { *v = g.sums[agg_idx]; return true; }
-      if (g.counts[agg_idx] <= 0) return false;                 /* NULL */
-      *v = ag.kind == SN_AGG_AVG ? g.sums[agg_idx] / g.counts[agg_idx]
-                                 : g.sums[agg_idx];
-      return true;
-    };
+  if (agg_idx >= 0)
     std::stable_sort(q->final_groups.begin(), q->final_groups.end(),
-                     [&](const GroupOut &a, const GroupOut &b) {
-                       double va, vb;
-                       bool ha = val_of(a, &va), hb = val_of(b, &vb);
-                       if (ha != hb) return ha;                 /* NULLs last */
-                       if (!ha) return false;
-                       /* a strict weak order with NaN in it: every NaN is
-                        * one value above +inf */
-                       const bool na = va != va, nb = vb != vb;
-                       if (na || nb) return descending ? na && !nb : nb && !na;
-                       return descending ? va > vb : va < vb;
-                     });
-  } else {
-    /* restore key order */
-    std::vector<GroupOut> groups = q->final_groups;
-    finalize_groups(q, groups);
-  }
+                     GroupValueLess{ agg_idx, p.aggs[agg_idx].kind,
+                                     descending != 0 });
+  else                                                /* restore key order */
+    std::sort(q->final_groups.begin(), q->final_groups.end(), GroupKeyLess());
   if (k > 0 && (int64_t)q->final_groups.size() > k)
     q->final_groups.resize((size_t)k);
   return SN_OK;
@@ -4258,24 +4207,20 @@ extern "C" int64_t sn_query_num_groups(sn_query *q) {
   if (q->select) return 0;
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
-  if (q->final_groups.empty() && !q->merged) {
-    if (q->sparse) {
-      /* count without materializing ~1M string-keyed GroupOuts — the
-       * multi-GPU capacity negotiation calls this every step (550 ms vs
-       * ~2 ms at 1M groups) */
-      const int naggs1 = (q->pac ? 2 : 1) * q->dev_naggs + 1;
-      int64_t n = 0;
-      for (size_t i = 0; i < q->sparse_n; i++)
-        n += q->sparse_rows[i * naggs1 + naggs1 - 1] != 0.0;
-      if (!q->sparse_null_row.empty() &&
-          q->sparse_null_row[naggs1 - 1] > 0.0)
-        n++;
-      return n;
-    }
-    std::vector<GroupOut> groups;
-    local_groups(q, &groups);
-    finalize_groups(q, groups);
+  if (q->sparse && !final_groups_ready(q)) {
+    /* count without materializing ~1M string-keyed GroupOuts — the
+     * multi-GPU capacity negotiation calls this every step (550 ms vs
+     * ~2 ms at 1M groups) */
+    const AccRowLayout L = row_layout(q);
+    const size_t width = (size_t)L.rowcount_at + 1;
+    int64_t n = 0;
+    for (size_t i = 0; i < q->sparse_n; i++)
+      n += acc_row_occupied(L, &q->sparse_rows[i * width]);
+    if (!q->sparse_null_row.empty())
+      n += acc_row_occupied(L, q->sparse_null_row.data());
+    return n;
   }
+  ensure_final_groups(q);
   return (int64_t)q->final_groups.size();
 }
 
@@ -4296,89 +4241,48 @@ extern "C" void sn_query_destroy(sn_query *q) {
   delete q;
 }
 
-/* ---- partial exchange ----
+/* ---- partial exchange (block format: partial_format.h) ----
  * Grouped blocks carry a caller-chosen slot CAPACITY (the *2 entry points):
  * group counts beyond SN_MAX_GROUP_SLOTS — the big dense-slot and sparse
  * hash-aggregate paths — export by negotiating a capacity across ranks
  * (e.g. allreduce-MAX of sn_query_num_groups) before the collective.  The
  * legacy entry points keep the fixed SN_MAX_GROUP_SLOTS capacity. */
-static int64_t partial_bytes_cap(sn_query *q, int32_t cap) {
-  if (q->plan.ngroup == 0 && !q->join_group)
-    return (int64_t)(2 * q->plan.naggs + 1) * 8;
-  return 8 + (int64_t)cap * sizeof(PartialSlot);
-}
-
-extern "C" int64_t sn_query_partial_bytes(sn_query *q) {
-  if (!q) return SN_ERR_BADARG;
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partial_bytes is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
-  if (q->dec)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partial_bytes is not supported on an exact decimal query (its "
-                "state is 128-bit fixed point, not the f64 partial layout)");
-  return partial_bytes_cap(q, SN_MAX_GROUP_SLOTS);
+static int64_t partial_bytes_cap(const sn_query *q, int32_t cap) {
+  return eff_ngroup(q) == 0 ? partial_keyless_bytes(q->plan.naggs)
+                            : partial_grouped_bytes(cap);
 }
 
 extern "C" int64_t sn_query_partial_bytes2(sn_query *q, int32_t cap_slots) {
   if (!q || cap_slots <= 0) return SN_ERR_BADARG;
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partial_bytes2 is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
-  if (q->dec)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partial_bytes2 is not supported on an exact decimal query (its "
-                "state is 128-bit fixed point, not the f64 partial layout)");
+  REFUSE_KIND(q, REFUSE_ROWS | REFUSE_DEC);
   return partial_bytes_cap(q, cap_slots);
+}
+
+extern "C" int64_t sn_query_partial_bytes(sn_query *q) {
+  return sn_query_partial_bytes2(q, SN_MAX_GROUP_SLOTS);
 }
 
 extern "C" int32_t sn_query_partials2(sn_query *q, void *dst,
                                       int32_t dst_is_device, int32_t cap_slots) {
   if (!q || !dst || cap_slots <= 0) return SN_ERR_BADARG;
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partials is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
-  if (q->dec)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partials is not supported on an exact decimal query (its "
-                "state is 128-bit fixed point, not the f64 partial layout)");
+  REFUSE_KIND(q, REFUSE_ROWS | REFUSE_DEC);
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
-  const sn_plan &p = q->plan;
+  std::vector<GroupOut> groups;
+  local_groups(q, &groups);
   std::vector<uint8_t> block((size_t)partial_bytes_cap(q, cap_slots), 0);
-  if (p.ngroup == 0 && !q->join_group) {
-    double *o = (double *)block.data();
-    const double *row = q->host_out.data();
-    for (int a = 0; a < p.naggs; a++) {
-      o[a] = row[a];
-      o[p.naggs + a] = q->pac ? row[p.naggs + a] : row[q->na_t + a];
-    }
-    o[2 * p.naggs] = row[2 * q->na_t];
+  if (eff_ngroup(q) == 0) {
+    partial_write_keyless(block.data(), groups[0], q->plan.naggs);
   } else {
-    std::vector<GroupOut> groups;
-    local_groups(q, &groups);
     if (groups.size() > (size_t)cap_slots)
       return fail(SN_ERR_OVERFLOW,
                   "%zu groups exceed the partial-block capacity %d "
                   "(negotiate a larger capacity via sn_query_partial_bytes2)",
                   groups.size(), cap_slots);
-    int32_t n = (int32_t)groups.size();
-    memcpy(block.data(), &n, 4);
-    memcpy(block.data() + 4, &cap_slots, 4);
-    PartialSlot *slots = (PartialSlot *)(block.data() + 8);
-    for (int32_t i = 0; i < n; i++) {
-      GroupOut &g = groups[i];
-      for (int k = 0; k < SN_MAX_GROUPS; k++) {
-        strncpy(slots[i].keys[k], g.keys[k].c_str(), SN_KEY_MAX - 1);
-        slots[i].key_null[k] = g.key_null[k] ? 1 : 0;
-      }
-      memcpy(slots[i].sums, g.sums, sizeof(g.sums));
-      memcpy(slots[i].counts, g.counts, sizeof(g.counts));
-      slots[i].rowcount = g.rowcount;
-    }
+    const int32_t n = (int32_t)groups.size();
+    partial_write_header(block.data(), n, cap_slots);
+    for (int32_t i = 0; i < n; i++)
+      partial_write_slot(block.data(), i, groups[(size_t)i]);
   }
   if (dst_is_device) {
     HIP_OR_FAIL(hipMemcpy(dst, block.data(), block.size(), hipMemcpyHostToDevice));
@@ -4397,60 +4301,30 @@ extern "C" int32_t sn_query_partials(sn_query *q, void *dst, int32_t dst_is_devi
  * only keys hashing to shard r; every other key's partial travels to its
  * owner (the reference's partial->final ShuffleExchange with hash
  * partitioning, SnappyStrategies.scala:560-601).  dst must hold
- * world * sn_query_partial_bytes(q) bytes; block d goes to rank d.  The
- * shard hash is FNV over the key bytes — layout-internal, any deterministic
- * function gives identical results. */
+ * world * sn_query_partial_bytes(q) bytes; block d goes to rank d. */
 extern "C" int32_t sn_query_partials_sharded2(sn_query *q, int32_t world,
                                               void *dst, int32_t cap_slots) {
   if (!q || !dst || world <= 0 || world > 1024 || cap_slots <= 0)
     return SN_ERR_BADARG;
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partials_sharded is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
-  if (q->dec)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_partials_sharded is not supported on an exact decimal query (its "
-                "state is 128-bit fixed point, not the f64 partial layout)");
-  const sn_plan &p = q->plan;
-  if (p.ngroup == 0 && !q->join_group) return SN_ERR_UNSUPPORTED;
+  REFUSE_KIND(q, REFUSE_ROWS | REFUSE_DEC);
+  const int ng = eff_ngroup(q);
+  if (ng == 0) return SN_ERR_UNSUPPORTED;
   int rc = sn_query_wait(q);
   if (rc != SN_OK) return rc;
-  int64_t bb = partial_bytes_cap(q, cap_slots);
+  const int64_t bb = partial_bytes_cap(q, cap_slots);
   memset(dst, 0, (size_t)bb * world);
   std::vector<GroupOut> groups;
   local_groups(q, &groups);
-  int eff_ngroup = q->join_group ? 1 + p.ngroup : p.ngroup;
   std::vector<int32_t> counts(world, 0);
-  for (auto &g : groups) {
-    uint64_t h = 1469598103934665603ull;
-    for (int k = 0; k < eff_ngroup; k++) {
-      if (g.key_null[k]) { h ^= 1; h *= 1099511628211ull; }
-      else
-        for (char c : g.keys[k]) { h ^= (uint8_t)c; h *= 1099511628211ull; }
-      h ^= 0xff; h *= 1099511628211ull;   /* key separator */
-    }
-    int d = (int)(h % (uint64_t)world);
-    uint8_t *bp = (uint8_t *)dst + (int64_t)d * bb;
-    int32_t &n = counts[d];
-    if (n >= cap_slots)
+  for (const GroupOut &g : groups) {
+    const int d = partial_shard_of(g, ng, world);
+    if (counts[d] >= cap_slots)
       return fail(SN_ERR_OVERFLOW,
                   "shard %d exceeds the partial-block capacity %d", d, cap_slots);
-    PartialSlot *slots = (PartialSlot *)(bp + 8);
-    for (int k = 0; k < SN_MAX_GROUPS; k++) {
-      strncpy(slots[n].keys[k], g.keys[k].c_str(), SN_KEY_MAX - 1);
-      slots[n].key_null[k] = g.key_null[k] ? 1 : 0;
-    }
-    memcpy(slots[n].sums, g.sums, sizeof(g.sums));
-    memcpy(slots[n].counts, g.counts, sizeof(g.counts));
-    slots[n].rowcount = g.rowcount;
-    n++;
+    partial_write_slot((uint8_t *)dst + (int64_t)d * bb, counts[d]++, g);
   }
-  for (int d = 0; d < world; d++) {
-    uint8_t *bp = (uint8_t *)dst + (int64_t)d * bb;
-    memcpy(bp, &counts[d], 4);
-    memcpy(bp + 4, &cap_slots, 4);
-  }
+  for (int d = 0; d < world; d++)
+    partial_write_header((uint8_t *)dst + (int64_t)d * bb, counts[d], cap_slots);
   return SN_OK;
 }
 
@@ -4459,72 +4333,22 @@ extern "C" int32_t sn_query_partials_sharded(sn_query *q, int32_t world,
   return sn_query_partials_sharded2(q, world, dst, SN_MAX_GROUP_SLOTS);
 }
 
+/* The blocks come from other ranks: all of them are checked against `stride`
+ * before the first is folded, and a refusal leaves the query as it was. */
 extern "C" int32_t sn_query_merge(sn_query *q, const void *blocks, int64_t stride,
                                   int32_t n_blocks) {
   if (!q || !blocks || n_blocks <= 0) return SN_ERR_BADARG;
-  if (q->select)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_merge is not supported on a row-returning query (its result is "
-                "rows, read with sn_rows_fetch)");
-  if (q->dec)
-    return fail(SN_ERR_UNSUPPORTED,
-                "sn_query_merge is not supported on an exact decimal query (its "
-                "state is 128-bit fixed point, not the f64 partial layout)");
-  const sn_plan &p = q->plan;
+  REFUSE_KIND(q, REFUSE_ROWS | REFUSE_DEC);
+  const AccRowLayout L = row_layout(q);
   std::vector<GroupOut> merged;
-  /* op-aware fold of one partial contribution into a GroupOut slot */
-  auto fold = [&](GroupOut &g, int a, double s, double c) {
-    int k = p.aggs[a].kind;
-    if (k == SN_AGG_MIN || k == SN_AGG_MAX) {
-      /* the aggregates' order: NaN above +inf (std::min/std::max would
-       * keep whichever side came first once a NaN is involved).  fmin
-       * returns the other side of a NaN, which is MIN's rule already. */
-      if (c > 0)
-        g.sums[a] = g.counts[a] <= 0 ? s
-                    : k == SN_AGG_MIN ? fmin(g.sums[a], s)
-                    : (g.sums[a] != g.sums[a] || s != s)
-                        ? std::numeric_limits<double>::quiet_NaN()
-                        : fmax(g.sums[a], s);
-    } else {
-      g.sums[a] += s;
-    }
-    g.counts[a] += c;
-  };
-  if (p.ngroup == 0 && !q->join_group) {
-    GroupOut g;
-    for (int32_t bi = 0; bi < n_blocks; bi++) {
-      const double *o = (const double *)((const uint8_t *)blocks + bi * stride);
-      for (int a = 0; a < p.naggs; a++) fold(g, a, o[a], o[p.naggs + a]);
-      g.rowcount += o[2 * p.naggs];
-    }
-    merged.push_back(g);
-  } else {
-    std::map<std::string, GroupOut> bykey;
-    for (int32_t bi = 0; bi < n_blocks; bi++) {
-      const uint8_t *bp = (const uint8_t *)blocks + bi * stride;
-      int32_t n; memcpy(&n, bp, 4);
-      const PartialSlot *slots = (const PartialSlot *)(bp + 8);
-      int eff_ngroup = q->join_group ? 1 + p.ngroup : p.ngroup;
-      for (int32_t i = 0; i < n; i++) {
-        std::string key;
-        for (int k = 0; k < eff_ngroup; k++) {
-          key += slots[i].key_null[k] ? std::string(1, '\x01')
-                                      : std::string(slots[i].keys[k]);
-          key += '\x00';
-        }
-        GroupOut &g = bykey[key];
-        for (int k = 0; k < eff_ngroup; k++) {
-          g.keys[k] = slots[i].keys[k];
-          g.key_null[k] = slots[i].key_null[k] != 0;
-        }
-        for (int a = 0; a < p.naggs; a++)
-          fold(g, a, slots[i].sums[a], slots[i].counts[a]);
-        g.rowcount += slots[i].rowcount;
-      }
-    }
-    for (auto &kv : bykey) merged.push_back(std::move(kv.second));
-  }
-  finalize_groups(q, merged);
+  int32_t bad = 0;
+  const int why = partial_merge(blocks, stride, n_blocks, eff_ngroup(q),
+                                L.naggs, L.kinds, &merged, &bad);
+  if (why != SN_PARTIAL_OK)
+    return fail(SN_ERR_BADARG,
+                "sn_query_merge: partial block %d of %d (stride %lld): %s",
+                bad, n_blocks, (long long)stride, partial_bad_text(why));
+  finalize_groups(q, std::move(merged));
   q->merged = true;
   return SN_OK;
 }

@@ -37,7 +37,7 @@ def build(force=False):
     srcdir = os.path.join(_DIR, "csrc")
     srcs = [os.path.join(srcdir, f) for f in
             ("engine.cpp", "builder.cpp", "jit.cpp", "kernels.hip",
-             "engine_internal.h")]
+             "engine_internal.h", "blob_format.h", "partial_format.h")]
     srcs.append(os.path.join(os.path.dirname(_DIR), "include",
                              "snappy_engine.h"))
     if force or (not os.path.exists(_SO)) or \
