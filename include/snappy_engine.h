@@ -368,6 +368,11 @@ int32_t   sn_query_used_jit(sn_query *q);
  * to keep few rows.  0 when no column was, SN_LATE=0 was set when the
  * engine was created, or the query ran interpreted.  Columns 0..62. */
 int64_t   sn_query_late_cols(sn_query *q);
+/* 1 when the late columns were read by the image-free ("direct") compiled
+ * kernel: a late plan of SUM/COUNT/AVG aggregates whose predicates are all
+ * ranges and whose other columns are INT32, INT16 or narrowed DOUBLE.  0
+ * otherwise, or with SN_DIRECT=0 set when the engine was created. */
+int32_t   sn_query_direct(sn_query *q);
 /* ORDER BY <aggregate value> [DESC] LIMIT k epilogue (SnappySortExec /
  * TakeOrderedAndProject semantics, core/.../SnappySortExec.scala): reorders
  * the finalized group rows by aggregate `agg_idx`'s value (NULLs last,

@@ -290,6 +290,12 @@ struct sn_engine {
    * rows.  SN_LATE=force engages whatever the estimate
    * (measurement only). */
   bool late = true, late_force = false;
+  /* SN_DIRECT (default on, 0 = off), read once per engine: a late plan with
+   * range predicates only, over int32/int16/narrowed columns, runs the
+   * image-free kernel.  SN_GRID_RESIDENT (default on, 0 =
+   * off): a keyless compiled kernel's grid comes from how many of its blocks
+   * the device holds at once instead of SN_GRID_CAP. */
+  bool direct = true, grid_resident = true;
   /* reusable per-engine scratch for block-partial reduction rows
    * (queries on one engine serialize on its stream) */
   double *scratch = nullptr;
@@ -370,6 +376,8 @@ extern "C" sn_engine *sn_engine_create(const sn_config *cfg) {
     e->late = lv[0] != '0';
     e->late_force = !strcmp(lv, "force");
   }
+  if (const char *dv = getenv("SN_DIRECT")) e->direct = dv[0] != '0';
+  if (const char *gv = getenv("SN_GRID_RESIDENT")) e->grid_resident = gv[0] != '0';
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && e->cfg.device >= 0) {
     if (hipSetDevice(e->cfg.device) == hipSuccess &&
@@ -1780,6 +1788,7 @@ struct sn_query {
   float kernel_ms = -1.0f;
   bool used_jit = false;                /* query-compiled kernel ran */
   int64_t late_cols = 0;                /* table columns it read late (bit c) */
+  int direct = 0;                       /* the image-free keyless kernel ran */
   bool done = false;
   bool merged = false;
   std::vector<GroupOut> final_groups;
@@ -2917,8 +2926,16 @@ static uint32_t tag_late_columns(const sn_query *q, const sn_dev_plan &dp,
   /* some staged column must remain to carry the predicates */
   if (!mask || !other) return 0;
   if (!e->late_force && !(estimate_selectivity(q) <= SN_LATE_MAX_SEL)) return 0;
+  /* the image-free kernel serves sums and counts under
+   * range predicates over columns it can test in a register or by code */
+  bool direct = e->direct && !q->mm && !dp.pac && dp.npreds_i == 0 &&
+                dp.npreds_in == 0;
+  for (int ui = 0; ui < dp.nused && direct; ui++)
+    direct = ((mask >> ui) & 1) || kinds[ui] == SN_K_I32 ||
+             kinds[ui] == SN_K_I16 || kinds[ui] == SN_K_F64C8;
   for (int ui = 0; ui < dp.nused; ui++)
-    if ((mask >> ui) & 1) kinds[ui] = SN_K_F64_LATE;
+    if ((mask >> ui) & 1)
+      kinds[ui] = direct ? SN_K_F64_LATE_DIRECT : SN_K_F64_LATE;
   return mask;
 }
 
@@ -2940,7 +2957,34 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
   /* one description of the launch, shared with sn_launch_scan_agg: scratch
    * holds the partial rows of whichever twin runs (interpreted or
    * compiled), or the 8 XCD-private copies of a global accumulator */
-  const sn_dense_launch d = sn_dense_launch_of(&dp, ntiles);
+  sn_dense_launch d = sn_dense_launch_of(&dp, ntiles);
+  /* query-compiled kernel (jit.cpp): plan constants baked as literals —
+   * the WholeStageCodegen analogue; measured 3x on Q1's shape over the
+   * interpreted runtime-plan kernel.  Any miss falls back, still on GPU. */
+  void *jfn = nullptr;
+  /* pac from ACTUAL nulls never reaches here (jit_ok excludes null
+   * batches); pac from MIN/MAX compiles op-aware kernels. */
+  uint32_t late = 0;
+  bool direct = false;
+  if (e->jit && sn_jit_shape_ok(&dp) && jit_inlists_ok(dp) && set.jit_ok) {
+    /* the late tag depends on this plan's predicate bounds, which the cached
+     * set's signature leaves out: it goes on a copy of the set's kinds */
+    int kinds[SN_DEV_MAX_COLS];
+    memcpy(kinds, set.jit_kinds, sizeof(kinds));
+    late = tag_late_columns(q, dp, kinds);
+    for (int ui = 0; ui < dp.nused; ui++)
+      direct |= kinds[ui] == SN_K_F64_LATE_DIRECT;
+    jfn = sn_jit_get(e->jit, &dp, kinds, dp.nslots, q->na_t, set.jit_del);
+  }
+  /* A keyless compiled kernel gets equal blocks in as few rounds as the
+   * device can hold at once: with SN_GRID_CAP blocks on a device that holds
+   * fewer, the last round runs part-filled.  d stays the one description:
+   * scratch and the reduce below follow d.grid_compiled. */
+  if (jfn && e->grid_resident && d.route == SN_ROUTE_KEYLESS) {
+    const int resident = sn_jit_resident(e->jit, jfn);
+    if (resident > 0 && resident <= SN_GRID_CAP)
+      d.grid_compiled = sn_balanced_grid(ntiles, resident);
+  }
   const size_t rows = (size_t)std::max(sn_dense_rows(&d, 0), sn_dense_rows(&d, 1));
   int rc = ensure_scratch(e, rows * d.nv * 8);
   if (rc != SN_OK) return rc;
@@ -2952,21 +2996,6 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
                          d.na1, dp_dev, e->stream) != 0)
     return fail(SN_ERR_GENERIC, "accumulator min/max init");
   acquire_events(q);
-  /* query-compiled kernel (jit.cpp): plan constants baked as literals —
-   * the WholeStageCodegen analogue; measured 3x on Q1's shape over the
-   * interpreted runtime-plan kernel.  Any miss falls back, still on GPU. */
-  void *jfn = nullptr;
-  /* pac from ACTUAL nulls never reaches here (jit_ok excludes null
-   * batches); pac from MIN/MAX compiles op-aware kernels. */
-  uint32_t late = 0;
-  if (e->jit && sn_jit_shape_ok(&dp) && jit_inlists_ok(dp) && set.jit_ok) {
-    /* the late tag depends on this plan's predicate bounds, which the cached
-     * set's signature leaves out: it goes on a copy of the set's kinds */
-    int kinds[SN_DEV_MAX_COLS];
-    memcpy(kinds, set.jit_kinds, sizeof(kinds));
-    late = tag_late_columns(q, dp, kinds);
-    jfn = sn_jit_get(e->jit, &dp, kinds, dp.nslots, q->na_t, set.jit_del);
-  }
   if (jfn)
     for (size_t ui = 0; ui < q->used_cols.size(); ui++)
       if (((late >> ui) & 1) && q->used_cols[ui] < 63)
@@ -2983,6 +3012,7 @@ static int32_t launch_dense(sn_query *q, const sn_dev_plan &dp,
                             q->dev_out, d.naggs1, d.out_stride,
                             dp_dev, e->stream);
     q->used_jit = rc == 0;
+    q->direct = rc == 0 && direct;
     if (rc != 0) jfn = nullptr;   /* interpreted kernels take over */
   }
   if (!jfn)
@@ -4001,6 +4031,10 @@ extern "C" int32_t sn_query_used_jit(sn_query *q) {
  * for the passing rows only (columns 0..62; 0 when none, or interpreted) */
 extern "C" int64_t sn_query_late_cols(sn_query *q) {
   return q && q->used_jit ? q->late_cols : 0;
+}
+
+extern "C" int32_t sn_query_direct(sn_query *q) {
+  return q && q->used_jit ? q->direct : 0;
 }
 
 /* number of compiled kernels in this engine's JIT cache (tokenized plan

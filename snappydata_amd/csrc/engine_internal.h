@@ -71,12 +71,16 @@ enum {
                         sidecar, not the blob), rle_vals = the batch's value
                         dictionary of rle_n <= 256 doubles, value =
                         rle_vals[body[row]] — bit for bit the f64 body's */
-  SN_K_F64_LATE = 13 /* JIT-only, never in a device descriptor (which keeps
+  SN_K_F64_LATE = 13,/* JIT-only, never in a device descriptor (which keeps
                         SN_K_F64 and the same body): a double column that only
                         aggregate factors use, in a keyless plan whose
                         predicates keep few rows.  The compiled kernel does
                         not stage it; it reads it in the row phase, for the
                         rows that pass alone. */
+  SN_K_F64_LATE_DIRECT = 14 /* JIT-only like SN_K_F64_LATE, and read the same
+                        way; selects the image-free keyless kernel (DESIGN.md
+                        §2d): the plan has range predicates only and every
+                        other used column is SN_K_I32, SN_K_I16 or SN_K_F64C8 */
 };
 
 typedef struct {
@@ -817,6 +821,9 @@ void sn_jit_cache_destroy(void *cache);
 int sn_jit_cache_count(void *cache);
 void *sn_jit_get(void *cache, const sn_dev_plan *p, const int *kinds,
                  int nslots, int na_t, int has_del);
+/* how many blocks of a kernel sn_jit_get returned the device holds at once
+ * (blocks per CU by the runtime's occupancy query x CUs); 0 when unknown */
+int sn_jit_resident(void *cache, void *fn);
 int sn_jit_launch(void *fn, int grid, const sn_dev_batch *batches,
                   const sn_dev_tile *tiles, int ntiles, double *scratch,
                   const int64_t *jkeys, const int32_t *jpayload,

@@ -43,6 +43,7 @@
 struct JitFn {
   hipModule_t mod = nullptr;
   hipFunction_t fn = nullptr;
+  int resident = 0;   /* blocks of fn the device holds at once; 0 = unknown */
 };
 
 struct JitCache {
@@ -79,6 +80,7 @@ static std::string strf(const char *fmt, ...) {
 
 #define JIT_CHUNK 1024          /* rows per LDS image chunk */
 #define JIT_WG 256
+#define JIT_DIRECT_SLOTS 8      /* rows per lane and step of the direct kernel */
 #define JIT_MAX_AGGS 12         /* sn_dev_plan.aggs */
 #define JIT_REG_MAX_SLOTS 8     /* most slots the per-lane registers carry */
 #define JIT_REG_MAX_AGGS 6      /* ... and most aggregates per slot */
@@ -128,6 +130,7 @@ struct JitShape {
   int nlate;         /* late columns: read in the row phase, passing rows only */
   int nstaged;       /* staged columns = rows of the LDS image */
   int lds_dict;      /* value dictionaries are looked up in an LDS copy */
+  int direct;        /* image-free row loop (SN_K_F64_LATE_DIRECT) */
   int late[SN_DEV_MAX_COLS];   /* column is late */
   int srow[SN_DEV_MAX_COLS];   /* a staged column's row of the LDS image */
 };
@@ -251,9 +254,12 @@ static JitShape jit_classify(const sn_dev_plan *p, const int *kinds,
   for (int i = 0; i < p->npreds_in && i < 2; i++)
     pred_cols |= 1u << p->inp[i].cslot;
   s.nlate = 0;
-  for (int c = 0; c < s.NC; c++)
-    s.nlate += s.late[c] = late_mode && kinds[c] == SN_K_F64_LATE &&
-                           !((pred_cols >> c) & 1);
+  int direct_tag = 0;
+  for (int c = 0; c < s.NC; c++) {
+    direct_tag |= kinds[c] == SN_K_F64_LATE_DIRECT;
+    s.nlate += s.late[c] = late_mode && !((pred_cols >> c) & 1) &&
+        (kinds[c] == SN_K_F64_LATE || kinds[c] == SN_K_F64_LATE_DIRECT);
+  }
   if (s.nlate == s.NC) {
     s.nlate = 0;
     for (int c = 0; c < s.NC; c++) s.late[c] = 0;
@@ -270,6 +276,11 @@ static JitShape jit_classify(const sn_dev_plan *p, const int *kinds,
     return !v || v[0] != '0';
   }();
   s.lds_dict = s.nlate > 0 && lds_dict_env;
+  /* The direct variant (SN_K_F64_LATE_DIRECT) goes by the tag
+   * alone; the engine sets it only on plans the row loop can serve.  It keeps
+   * no image, so its LDS is a few KB and the wave count bounds residency. */
+  s.direct = direct_tag && s.nlate > 0 && s.acc == ACC_KEYLESS;
+  if (s.direct) s.lds_dict = 0;   /* it keeps its own copy */
   return s;
 }
 
@@ -308,7 +319,7 @@ static const JitKind &jit_kind(int k) {
   static const JitKind c8 = { "unsigned short", 1, "unsigned char", CV_VDICT,
                               0, 0 };
   switch (k) {
-    case SN_K_F64: case SN_K_F64_LATE: return f64;
+    case SN_K_F64: case SN_K_F64_LATE: case SN_K_F64_LATE_DIRECT: return f64;
     case SN_K_I64: return i64;
     case SN_K_I32: return i32;
     case SN_K_F32: return f32;
@@ -866,15 +877,20 @@ static void emit_radix_stash(Gen &g) {
     emitf(g.o, "      double rva%d[CHUNK / WG];\n", a);
 }
 
+/* the row's delete bit (row base + r of the batch) */
+static void emit_delete_pred(Gen &g) {
+  if (g.has_del)
+    g.o += "        if (del) {\n"
+           "          const int gr = base + r;\n"
+           "          ok &= (int)(~(del[(u64)gr >> 6] >> (gr & 63)) & 1ull);\n"
+           "        }\n";
+}
+
 /* row predicates: delete mask, range predicates, bitmap IN-lists */
 static void emit_row_predicates(Gen &g) {
   std::string &o = g.o;
   const sn_dev_plan *p = g.p;
-  if (g.has_del)
-    o += "        if (del) {\n"
-         "          const int gr = base + r;\n"
-         "          ok &= (int)(~(del[(u64)gr >> 6] >> (gr & 63)) & 1ull);\n"
-         "        }\n";
+  emit_delete_pred(g);
   for (int i = 0; i < p->npreds_d; i++) {
     emitf(o, "        { const double x = sval[%d][r];\n"
              "          ok &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n",
@@ -1066,6 +1082,156 @@ static void emit_slot(Gen &g) {
   }
 }
 
+/* ---- the direct (image-free) keyless kernel: DESIGN.md §2d --------------
+ * No LDS image and no barrier in the row loop.  Per tile each workgroup
+ * copies the value dictionaries that aggregate factors read (svd<c>) and
+ * evaluates every narrowed predicate column's range predicates once, on its
+ * dictionary, into a 256-bit pass set (spass<c>).  Both are double-buffered
+ * by tile parity (pb), so the one barrier per tile orders the writes before
+ * the reads, and the reads of tile n before the writes of tile n + 2.  A
+ * lane then handles DS rows per step, row = base + tid + k * WG: the staged
+ * loads of all DS rows are issued together (and the next step's before this
+ * step's late values are used), integer columns compare in registers, a
+ * narrowed predicate column tests its code's bit, and the late loads of the
+ * DS rows fly together. */
+
+static bool direct_has_pred(const Gen &g, int c) {
+  for (int i = 0; i < g.p->npreds_d; i++)
+    if (g.p->preds_d[i].cslot == c) return true;
+  return false;
+}
+
+static bool direct_is_factor(const Gen &g, int c) {
+  for (int a = 0; a < g.s.NA; a++) {
+    const sn_dev_agg &A = g.p->aggs[a];
+    if ((A.nf >= 1 && A.c0 == c) || (A.nf >= 2 && A.c1 == c) ||
+        (A.nf >= 3 && A.c2 == c))
+      return true;
+  }
+  return false;
+}
+
+/* an aggregate factor of a column that is not late: f<c>[k] is the row's
+ * code or integer, kept from the staged registers */
+static std::string direct_factor(const Gen &g, int cs) {
+  return jit_kind(g.kinds[cs]).conv == CV_VDICT
+             ? strf("svd%d[pb][f%d[k]]", cs, cs)
+             : strf("(double)f%d[k]", cs);
+}
+
+static const char *direct_reg_type(const JitKind &K) {
+  return K.conv == CV_VDICT ? "unsigned" : "int";
+}
+
+static void emit_direct_decl(Gen &g) {
+  std::string &o = g.o;
+  const JitShape &s = g.s;
+  static_assert(JIT_WG == SN_NARROW_MAX, "one dictionary entry per lane");
+  for (int c = 0; c < s.NC; c++) {
+    if (jit_kind(g.kinds[c]).conv != CV_VDICT) continue;
+    if (direct_is_factor(g, c))
+      emitf(o, "  __shared__ __attribute__((aligned(16))) double svd%d[2][WG];\n", c);
+    if (direct_has_pred(g, c))
+      emitf(o, "  __shared__ __attribute__((aligned(16))) u64 spass%d[2][4];\n", c);
+  }
+  emitf(o, "  __shared__ __attribute__((aligned(16))) double bacc[%d];\n", s.nv);
+  o += "  const int tid = threadIdx.x;\n";
+  emitf(o, "  double sums[%d], cnts[%d], rcnt = 0.0;\n", s.NA, s.NA);
+  emitf(o, "#pragma unroll\n  for (int a = 0; a < %d; a++) { sums[a] = 0; cnts[a] = 0; }\n", s.NA);
+  o += "  int pb = 0;\n";
+  for (int c = 0; c < s.NC; c++)
+    if (!s.late[c])
+      emitf(o, "  %s x%d[DS];\n", direct_reg_type(jit_kind(g.kinds[c])), c);
+}
+
+/* per tile: dictionaries and pass sets into the pb half, one barrier */
+static void emit_direct_dicts(Gen &g) {
+  std::string &o = g.o;
+  const sn_dev_plan *p = g.p;
+  for (int c = 0; c < g.s.NC; c++) {
+    if (jit_kind(g.kinds[c]).conv != CV_VDICT) continue;
+    if (direct_is_factor(g, c))
+      emitf(o, "    svd%d[pb][tid] = vd%d[tid];\n", c, c);
+    if (!direct_has_pred(g, c)) continue;
+    /* entries past the batch's count are 0.0 and no code names them */
+    emitf(o, "    { const double x = vd%d[tid];\n"
+             "      int in = 1;\n", c);
+    for (int i = 0; i < p->npreds_d; i++)
+      if (p->preds_d[i].cslot == c)
+        emitf(o, "      in &= (x >= pd%d_lo) & (x <= pd%d_hi);\n", i, i);
+    emitf(o, "      const u64 m = __ballot(in);\n"
+             "      if ((tid & 63) == 0) spass%d[pb][tid >> 6] = m; }\n", c);
+  }
+  o += "    __syncthreads();\n";
+  for (int c = 0; c < g.s.NC; c++)
+    if (jit_kind(g.kinds[c]).conv == CV_VDICT && direct_has_pred(g, c))
+      emitf(o, "    const unsigned *pw%d = (const unsigned *)spass%d[pb];\n", c, c);
+}
+
+/* the staged loads of DS rows per lane from `base_expr`, for a step that
+ * holds at least one row.  Addresses are the step's uniform base plus a lane
+ * offset below DS * WG, so each load takes one 32-bit offset register.  The
+ * lane offset is clamped to the tile's last row, so every lane loads inside
+ * the column body without a branch; `ok` drops the clamped rows.  (A second,
+ * unclamped copy of the loads for whole steps cost registers: with it the
+ * 4-slot kernel spilled at 64 VGPRs.) */
+static void emit_direct_load(Gen &g, const char *base_expr, const char *ind) {
+  std::string &o = g.o;
+  emitf(o, "%sif (%s < tile_end) {\n"
+           "#pragma unroll\n"
+           "%s  for (int k = 0; k < DS; k++) {\n"
+           "%s    const unsigned rr = min((unsigned)(tid + k * WG),\n"
+           "%s                            (unsigned)(tile_end - 1 - (%s)));\n",
+        ind, base_expr, ind, ind, ind, base_expr);
+  for (int c = 0; c < g.s.NC; c++) {
+    if (g.s.late[c]) continue;
+    const JitKind &K = jit_kind(g.kinds[c]);
+    emitf(o, "%s    x%d[k] = ((const GAS %s *)(body%d + (u64)(%s) * %d))[rr];\n",
+          ind, c, K.mem, c, base_expr, K.bytes);
+  }
+  emitf(o, "%s  }\n%s}\n", ind, ind);
+}
+
+/* pass A of a step: every slot's `ok`, the factor inputs kept, and the late
+ * loads issued under `ok` (the contract of emit_late_stash) */
+static void emit_direct_pass_a(Gen &g) {
+  std::string &o = g.o;
+  const sn_dev_plan *p = g.p;
+  o += "      int okv[DS];\n";
+  for (int c = 0; c < g.s.NC; c++) {
+    if (g.s.late[c]) emitf(o, "      double e%d[DS];\n", c);
+    else if (direct_is_factor(g, c))
+      emitf(o, "      %s f%d[DS];\n", direct_reg_type(jit_kind(g.kinds[c])), c);
+  }
+  o += "#pragma unroll\n"
+       "      for (int k = 0; k < DS; k++) {\n"
+       "        const int r = tid + k * WG;\n"
+       "        int ok = base + r < tile_end;\n";
+  emit_delete_pred(g);
+  for (int c = 0; c < g.s.NC; c++) {
+    if (g.s.late[c] || !direct_has_pred(g, c)) continue;
+    if (jit_kind(g.kinds[c]).conv == CV_VDICT) {
+      emitf(o, "        ok &= (int)((pw%d[x%d[k] >> 5] >> (x%d[k] & 31u)) & 1u);\n",
+            c, c, c);
+      continue;
+    }
+    for (int i = 0; i < p->npreds_d; i++)
+      if (p->preds_d[i].cslot == c)
+        emitf(o, "        { const double x = (double)x%d[k];\n"
+                 "          ok &= (x >= pd%d_lo) & (x <= pd%d_hi); }\n", c, i, i);
+  }
+  o += "        okv[k] = ok;\n";
+  for (int c = 0; c < g.s.NC; c++) {
+    if (g.s.late[c])
+      emitf(o, "        e%d[k] = 0.0;\n"
+               "        if (ok) e%d[k] = ((const GAS double *)(body%d + (u64)base * 8))[r];\n",
+            c, c, c);
+    else if (direct_is_factor(g, c))
+      emitf(o, "        f%d[k] = x%d[k];\n", c, c);
+  }
+  o += "      }\n";
+}
+
 /* va<a>: each aggregate's input value for this row */
 static void emit_agg_values(Gen &g) {
   std::string &o = g.o;
@@ -1073,6 +1239,7 @@ static void emit_agg_values(Gen &g) {
    * convert only for those slots (compile-time; i64_mask is in the shape) */
   auto factor = [&](int a, int i, int cs, double fa, double fm) {
     const std::string f = g.s.late[cs] ? strf("e%d[k]", cs)
+        : g.s.direct ? direct_factor(g, cs)
         : plan_col_is_i64(g.p, cs)
         ? strf("(double)__double_as_longlong(sval[%d][r])", g.s.srow[cs])
         : strf("sval[%d][r]", g.s.srow[cs]);
@@ -1277,6 +1444,61 @@ static void emit_flush(Gen &g) {
   o += "}\n";
 }
 
+/* rows per lane and step of the direct kernel.  SN_DIRECT_SLOTS (4, 8 or
+ * 16) and SN_DIRECT_PREFETCH=0 exist for the measurements of DESIGN.md §2d;
+ * both are read once per process, before the first kernel is generated. */
+static int direct_slots(void) {
+  static const int v = [] {
+    const char *e = getenv("SN_DIRECT_SLOTS");
+    const int n = e ? atoi(e) : 0;
+    return n == 4 || n == 8 || n == 16 ? n : JIT_DIRECT_SLOTS;
+  }();
+  return v;
+}
+static int direct_prefetch(void) {
+  static const int v = [] {
+    const char *e = getenv("SN_DIRECT_PREFETCH");
+    return !e || e[0] != '0';
+  }();
+  return v;
+}
+
+/* the direct kernel: the same prelude, signature, literals, tile head,
+ * value expressions, accumulate and flush as every keyless kernel; its own
+ * declarations, per-tile dictionary work and row loop */
+static void gen_direct(Gen &g) {
+  std::string &o = g.o;
+  /* waves traded for registers: 8 slots with the next step's loads in
+   * flight take about 100 VGPRs, that is 4 waves per SIMD, and measured
+   * faster than 4 slots in 64 VGPRs at 8 waves */
+  g.s.occupancy = 32 / direct_slots();
+  emitf(o, "#define DS %d\n", direct_slots());
+  emit_signature(g);
+  emit_literals(g);
+  emit_direct_decl(g);
+  emit_tile_prologue(g);
+  emit_direct_dicts(g);
+  emit_direct_load(g, "tile.row_start", "    ");
+  o += "    for (int base = tile.row_start; base < tile_end; base += DS * WG) {\n";
+  emit_direct_pass_a(g);
+  o += "      const int nbase = base + DS * WG;\n";
+  /* behind the late loads in issue order: waiting for those leaves the next
+   * step's staged loads in flight */
+  if (direct_prefetch()) emit_direct_load(g, "nbase", "      ");
+  o += "#pragma unroll\n"
+       "      for (int k = 0; k < DS; k++) {\n"
+       "        const int ok = okv[k];\n"
+       "        if (__popcll(__ballot(ok)) == 0) continue;\n";
+  emit_agg_values(g);
+  emit_accumulate(g);
+  o += "      }\n";
+  if (!direct_prefetch()) emit_direct_load(g, "nbase", "      ");
+  o += "    }\n"
+       "    pb ^= 1;\n"
+       "  }\n";
+  emit_flush(g);
+}
+
 /* Generate the specialized kernel source.
  * kinds[c]: SN_K_* per used column slot (uniform across batches).
  * Layout contract identical to the interpreted kernels:
@@ -1301,6 +1523,10 @@ static std::string gen_source(const sn_dev_plan *p, const int *kinds,
             offsetof(sn_dev_col, rle_vals));
       break;
     }
+  if (g.s.direct) {
+    gen_direct(g);
+    return std::move(g.o);
+  }
   emit_order_helpers(g);
   emit_signature(g);
   emit_literals(g);
@@ -1462,8 +1688,28 @@ extern "C" void *sn_jit_get(void *cache, const sn_dev_plan *p,
     (void)hipModuleUnload(jf.mod);
     return nullptr;
   }
+  /* blocks of this kernel the device holds at once: the keyless launch
+   * sizes its grid by it.  Left 0 (the caller keeps its own grid) when the
+   * runtime cannot say. */
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, jf.fn, JIT_WG,
+                                                         0) == hipSuccess &&
+      per_cu > 0 && hipGetDevice(&dev) == hipSuccess &&
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                            dev) == hipSuccess && cus > 0)
+    jf.resident = per_cu * cus;
   jc->fns[h] = jf;
   return (void *)jf.fn;
+}
+
+/* resident blocks of a kernel sn_jit_get returned; 0 when unknown */
+extern "C" int sn_jit_resident(void *cache, void *fn) {
+  auto *jc = (JitCache *)cache;
+  if (!jc || !fn) return 0;
+  std::lock_guard<std::mutex> g(jc->mu);
+  for (const auto &kv : jc->fns)
+    if ((void *)kv.second.fn == fn) return kv.second.resident;
+  return 0;
 }
 
 extern "C" int sn_jit_cache_count(void *cache) {

@@ -94,6 +94,8 @@ def lib():
         L.sn_query_used_jit.argtypes = [C.c_void_p]
         L.sn_query_late_cols.restype = C.c_int64
         L.sn_query_late_cols.argtypes = [C.c_void_p]
+        L.sn_query_direct.restype = C.c_int32
+        L.sn_query_direct.argtypes = [C.c_void_p]
         L.sn_query_order_by.restype = C.c_int32
         L.sn_query_order_by.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int64]
@@ -381,6 +383,13 @@ class Query:
         was created."""
         m = int(lib().sn_query_late_cols(self._h))
         return [c for c in range(63) if (m >> c) & 1]
+
+    def direct(self):
+        """1 when the late columns were read by the image-free compiled
+        kernel (range predicates only, over INT32/INT16/narrowed DOUBLE
+        columns); 0 otherwise, or with SN_DIRECT=0 in the environment when
+        the engine was created."""
+        return int(lib().sn_query_direct(self._h))
 
     def order_by(self, agg_idx, descending=False, k=0):
         """ORDER BY <aggregate value> [DESC] LIMIT k epilogue
